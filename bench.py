@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the flashpca PCA hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W          (N=1 directly; N>1 under torch.distributed.run)
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]   (N=1 directly; N>1 under torch.distributed.run)
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, dtype, config).
+`--full` adds everything else the line carries below: the instrumented steps and the roofline, the child profiler runs, the side
+measurements, the PCA solves, the other arithmetic modes, the CLI run, the CPU baseline and, with several ranks, the self-validation.
+`--dump-outputs DIR` writes what the last timed step computed (DIR/Y.npy, see dump_outputs).
 
 A "step" is ONE pass of the hot path over the resident genotype matrix: the block operator
 Y = sum_g X_g X_g' B on b columns, i.e. K2 (xt_b) + K3 (x_t) + the all-reduce of the N x b product when N > 1.  That is b
@@ -22,10 +27,10 @@ sample counts): the per-GPU compute of the 8-GPU runs, measurable on one GPU.
 
 Arithmetic: `--accum i8` (default; the product's default FPCA_ACCUM_AUTO resolves to it) runs the two GEMMs on the int8 matrix
 cores -- integer genotype matrices x byte slices of the fp64 operand, exact int32 accumulation, fp64 recombination
--- with results equal to the fp64 MFMA kernels (`--accum fp64`) to ~3e-15; the line carries the other mode's timing and the
-measured difference between the two as `fp64_mode` / `exact_int8_mode`.
+-- with results equal to the fp64 MFMA kernels (`--accum fp64`) to ~3e-15; the `--full` line carries the other mode's timing and
+the measured difference between the two as `fp64_mode` / `exact_int8_mode`.
 
-The same JSON line also carries: the roofline of the dominant kernel (HIP events recorded live on the
+The `--full` line also carries: the roofline of the dominant kernel (HIP events recorded live on the
 kernels' stream inside the timed region), a bounded CPU baseline (the oracle = restated reference path, one
 thread, like the shipped reference), and the wall-clock of one full k=20 PCA solve to convergence.
 """
@@ -81,9 +86,9 @@ def _child(args, prof_args, steps, tmp):
 
     cmd = ["rocprofv3"] + prof_args + ["--output-format", "csv", "-d", tmp, "-o", "pmc", "--", sys.executable,
            os.path.abspath(__file__), "--workload", args.workload, "--accum", args.accum, "--blockvec", str(args.blockvec),
-           "--steps", str(steps), "--warmup", "1", "--no-cpu-baseline", "--no-pca", "--no-alt", "--no-e2e", "--no-cheap", "--traffic", "none"]
+           "--steps", str(steps), "--warmup", "1"]  # (a plain run: block applies only)
     subprocess.run(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=150, check=True,  # (a healthy child takes ~10 s)
-                   env={k: v for k, v in dict(os.environ, TMPDIR="/tmp").items() if k != "LD_PRELOAD"})
+                   env=dict(os.environ, TMPDIR="/tmp"))
     pat = "*kernel_trace.csv" if "--pmc" not in prof_args else "*counter_collection.csv"
     fs = glob.glob(os.path.join(tmp, "**", pat), recursive=True)
     if not fs:
@@ -294,6 +299,41 @@ def e2e_size_auto(N, P):
     return "cfg3" if (free > 2.2 * need and mem > 3 * need) else "cfg2"
 
 
+DUMP_MAX_VALUES = 1 << 22  # 32 MiB of float64
+
+
+def dump_outputs(d, Y, N, b):
+    """DIR/Y.npy: the N x b product X X' B of the last timed step as fpca_apply_xxt_dev's caller holds it (float64, without the
+    padding rows); when that exceeds DUMP_MAX_VALUES, the rows of a fixed, seeded sample in ascending order"""
+    import numpy as np
+    import torch
+
+    rows = min(N, DUMP_MAX_VALUES // b)
+    if rows < N:
+        idx = np.sort(np.random.default_rng(0).choice(N, rows, replace=False))
+        Yh = Y[torch.as_tensor(idx, device=Y.device)]
+    else:
+        Yh = Y[:N]
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "Y.npy"), Yh.cpu().numpy())
+
+
+def finish(out, rank, world, ctx):
+    if rank == 0:
+        # anything the C side buffered on stdout (RCCL prints a version banner there under NCCL_DEBUG=VERSION) goes out first:
+        # the JSON line is the last line of rank 0's stdout
+        import ctypes
+
+        ctypes.CDLL(None).fflush(None)
+        sys.stdout.flush()
+        print(json.dumps(out), flush=True)
+    ctx.close()
+    if world > 1:
+        import torch.distributed as dist
+
+        dist.destroy_process_group()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -322,6 +362,12 @@ def main():
                     help="roofline.traffic: measure = two extra rocprofv3 --pmc passes (FETCH_SIZE; WRITE_SIZE) of a 2-step run of the "
                          "same workload as child processes after the timed region; replay = the committed passes under profiles/; "
                          "auto = measure when rocprofv3 is there and this is a one-GPU run, else replay")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything else the line can carry (roofline, profiler child runs, side "
+                         "measurements, PCA solves, other modes, CLI run, CPU baseline, multi-rank validation); the --no-* / --traffic / "
+                         "--e2e-size / --cpu-seconds options shape that part")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/Y.npy (float64; see dump_outputs)")
     args = ap.parse_args()
 
     # the host driver of these boxes only supports dmabuf IPC; RCCL across processes needs this (already exported there)
@@ -456,6 +502,30 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, Y, N, b)
+
+    # SNPs all ranks processed per step (the shard workloads process one shard; their divisor is the full matrix's)
+    P_done = P_rank * world if w["scaling"] == "weak" else P_total
+    cells = float(N) * float(P_done) * b * args.steps
+    value = cells / elapsed
+    out = dict(metric="genotype cells/sec (N x P x iters) for k=20 PCA", value=value, unit="cells/s", n_gpus=world,
+               steps=args.steps, warmup=args.warmup, spinup_applies=SPINUP[args.workload],
+               ms_per_step=elapsed / args.steps * 1e3, higher_is_better=True,
+               scaling=w["scaling"], vs_baseline=None,
+               dtype={"fp64": "f64", "fp32": "f32 (fp64 long accumulation)"}.get(
+                   args.accum, "i8 (integer genotypes x 7 byte slices of the f64 operand; exact i32 accumulation, f64 recombination; "
+                               "agrees with the f64 kernels to ~3e-15, see fp64_mode)"),
+               data="synthetic",
+               config=dict(workload=args.workload + ": " + w["desc"], samples=N, snps_total=P_total, snps_per_gpu=P_rank,
+                           k=k, blockvec=b, solver_default_blockvec=solver_blockvec(k), missing_call_rate=0.001, parallelism="snp-shard x%d + all-reduce(N x b) [%s]" % (world, transport),
+                           iters_per_step=b, generate_s=round(t_gen, 3),
+                           solver_passes="`value` and every fpca_apply_* call: exact (7 slices).  fpca_pca (`pca*` blocks): exact passes until the measured "
+                                         "decay predicts a long solve, then 4-slice passes verified by exact ones (see cheap_applies there)"))
+    if not args.full:
+        finish(out, rank, world, ctx)
+        return
+
     # Right after it, an INSTRUMENTED region of the same applies: in-stream HIP events (on the kernels' own stream) around K2 /
     # K3 / their GEMM kernels / the all-reduce of every step.  Eight events per apply stretch a step by a few per cent, which
     # is why they are not in the region that sets `value`; the per-kernel times below belong to THESE steps
@@ -469,11 +539,6 @@ def main():
     barrier()
     elapsed_i = time.perf_counter() - t0i
     prof = ctx.profile_end(b)
-
-    # SNPs all ranks processed per step (the shard workloads process one shard; their divisor is the full matrix's)
-    P_done = P_rank * world if w["scaling"] == "weak" else P_total
-    cells = float(N) * float(P_done) * b * args.steps
-    value = cells / elapsed
 
     _peaks = {}
 
@@ -585,20 +650,7 @@ def main():
             except Exception:
                 continue
 
-    out = dict(metric="genotype cells/sec (N x P x iters) for k=20 PCA", value=value, unit="cells/s", n_gpus=world,
-               steps=args.steps, warmup=args.warmup, spinup_applies=SPINUP[args.workload],
-               ms_per_step=elapsed / args.steps * 1e3, higher_is_better=True,
-               scaling=w["scaling"], vs_baseline=None,
-               dtype={"fp64": "f64", "fp32": "f32 (fp64 long accumulation)"}.get(
-                   args.accum, "i8 (integer genotypes x 7 byte slices of the f64 operand; exact i32 accumulation, f64 recombination; "
-                               "agrees with the f64 kernels to ~3e-15, see fp64_mode)"),
-               data="synthetic",
-               config=dict(workload=args.workload + ": " + w["desc"], samples=N, snps_total=P_total, snps_per_gpu=P_rank,
-                           k=k, blockvec=b, solver_default_blockvec=solver_blockvec(k), missing_call_rate=0.001, parallelism="snp-shard x%d + all-reduce(N x b) [%s]" % (world, transport),
-                           iters_per_step=b, generate_s=round(t_gen, 3),
-                           solver_passes="`value` and every fpca_apply_* call: exact (7 slices).  fpca_pca (`pca*` blocks): exact passes until the measured "
-                                         "decay predicts a long solve, then 4-slice passes verified by exact ones (see cheap_applies there)"),
-               roofline=roofline)
+    out["roofline"] = roofline
 
     # ---- what the realistic solves actually run: the eigensolver's CHEAP passes (block apply on 4 byte slices of the operand: the
     # 2-column-tile instantiation of the int8 GEMM; 128 of the 141 passes of pca_realistic, 137 of 150 of pca_hard_spectrum) -- its own
@@ -1115,19 +1167,9 @@ def main():
     rl["missing_2pct_slowdown"] = _g(out, "apply_at_missing_2pct", "slowdown_vs_value")
     rl["missing_2pct_cheap_pass_ms"] = _g(out, "apply_at_missing_2pct", "cheap_pass_ms_per_step")
 
-    if rank == 0:
-        # anything the C side buffered on stdout (RCCL prints a version banner there under NCCL_DEBUG=VERSION) goes out first:
-        # the JSON line is the last line of rank 0's stdout
-        import ctypes
-
-        ctypes.CDLL(None).fflush(None)
-        sys.stdout.flush()
-        print(json.dumps(out), flush=True)
     if whole is not None:
         whole.close()
-    ctx.close()
-    if world > 1:
-        dist.destroy_process_group()
+    finish(out, rank, world, ctx)
 
 
 if __name__ == "__main__":

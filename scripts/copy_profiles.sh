@@ -1,5 +1,5 @@
-# copies the summaries of gpurun_out/<round>/ (written by gpu_profile_round.sh on the GPU box) into profiles/:  bash scripts/copy_profiles.sh r02
-R=${1:-r05}; S=gpurun_out/$R; D=profiles
+# copies the summaries of ${OUT:-results}/<round>/ (written by gpu_profile_round.sh) into profiles/:  bash scripts/copy_profiles.sh r02
+R=${1:-r05}; S=${OUT:-results}/$R; D=profiles
 for f in $S/bench_*.json; do [ -s $f ] && cp $f $D/${R}_$(basename $f); done
 for wl in cfg2 cfg3 cfg4shard; do for a in i8 fp64; do
   f=$(ls $S/trace_${wl}_$a/*kernel_stats.csv 2>/dev/null | head -1); [ -n "$f" ] && cp $f $D/${R}_bench_${wl}_${a}_kernel_stats.csv

@@ -1,5 +1,5 @@
 """bench.py is what the driver runs: its one JSON line must keep its contract -- the metric of BASELINE.json, value = cells over
-the timed region, `roofline` and `cpu_baseline` objects -- and, with several ranks, validate itself.  Run here on the smoke-size
+the timed region; with --full also `roofline` and `cpu_baseline` objects and, with several ranks, a self-validation.  Run here on the smoke-size
 workload (seconds), single rank and as two ranks sharing the one GPU over gloo (the plumbing path of a multi-GPU run; the native
 RCCL communicator refuses two ranks on one device, so the torch.distributed hook transport carries it)."""
 import json
@@ -22,7 +22,7 @@ def last_json_line(text):
 
 def test_bench_line_contract_single_rank():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "20", "--warmup", "3", "--cpu-seconds", "2",
-                        "--no-e2e", "--traffic", "none"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--no-e2e", "--traffic", "none", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     assert r.stdout.strip().splitlines()[-1].startswith("{")  # the JSON line is the LAST line of stdout
     d = last_json_line(r.stdout)
@@ -57,6 +57,43 @@ def test_bench_line_contract_single_rank():
         assert rf["cheap_pass_ms"] == d["cheap_pass"]["ms_per_step"]
 
 
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run carries the headline only, times exactly --steps steps, and --dump-outputs writes the product of the last one."""
+    import numpy as np
+
+    import flashpca_amd as fp
+
+    # bench.py run as itself, with every call of the hot path counted: spin-up + warm-up + the timed steps, nothing else
+    counted = ("import os, runpy, sys; sys.path.insert(0, os.getcwd()); import flashpca_amd as fp; n = [0]; f = fp.Context.apply_xxt_dev\n"
+               "def g(*a, **k):\n    n[0] += 1\n    return f(*a, **k)\n"
+               "fp.Context.apply_xxt_dev = g; sys.argv = ['bench.py'] + sys.argv[1:]; runpy.run_path('bench.py', run_name='__main__')\n"
+               "print('applies', n[0], file=sys.stderr)")
+    r = subprocess.run([sys.executable, "-c", counted, "--workload", "tiny", "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = last_json_line(r.stdout)
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["unit"] == "cells/s" and d["higher_is_better"] is True
+    assert r.stderr.strip().splitlines()[-1] == "applies %d" % (d["spinup_applies"] + 2 + 7)
+    assert not {"roofline", "cpu_baseline", "pca", "fp64_mode", "cheap_pass", "e2e_cli"} & set(d)
+    cfg = d["config"]
+    N, b = cfg["samples"], cfg["blockvec"]
+    assert abs(d["value"] - N * cfg["snps_total"] * b * 7 / (d["ms_per_step"] * 1e-3 * 7)) <= 1e-6 * d["value"]
+    Y = np.load(tmp_path / "Y.npy")
+    assert Y.dtype == np.float64 and Y.shape == (N, b)
+    # the same block (bench.py's seeded generator) through the host-pointer entry point of a fresh context on the same matrix; torch
+    # draws it in a child process: torch brings its own HIP runtime and librccl, which would shadow the system RCCL that later tests
+    # of this process load
+    gen = ("import sys, numpy as np, torch; g = torch.Generator(device='cuda'); g.manual_seed(1234); "
+           "np.save(sys.argv[3], (torch.rand((int(sys.argv[1]), int(sys.argv[2])), dtype=torch.float64, device='cuda', generator=g) - 0.5).cpu().numpy())")
+    subprocess.run([sys.executable, "-c", gen, str(N), str(b), str(tmp_path / "B.npy")], check=True, timeout=300)
+    B = np.load(tmp_path / "B.npy")
+    with fp.Context.synthetic(N, cfg["snps_per_gpu"], n_pop=min(2 * cfg["k"], 64), accum="i8") as c:
+        c.set_total_snps(cfg["snps_total"])
+        c.stats()
+        Z = c.apply_xxt(B)
+    assert np.max(np.abs(Y - Z)) <= 1e-12 * np.max(np.abs(Z))
+
+
 def test_bench_two_ranks_on_one_gpu_validates_itself():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -64,7 +101,8 @@ def test_bench_two_ranks_on_one_gpu_validates_itself():
     s.close()
     env = dict(os.environ, FPCA_BENCH_BACKEND="gloo", FPCA_BENCH_ONE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--workload", "tiny"],
+                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--workload", "tiny",
+                        "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
     d = last_json_line(r.stdout)
