@@ -1299,15 +1299,13 @@ __global__ __launch_bounds__(256) void k_gram_tiled(const double *const *__restr
 
 // basis blocks that share one W tile, by block width (accumulators: QG NT^2 x 8 registers)
 static inline int gram_group(int b) { return b == 16 ? 8 : b == 32 ? 2 : 1; }
-static int g_k4_variant = 1; // fpca_debug_k4_variant: 0 = round 4's kernels (one basis block per workgroup row / C from L1), 1 = tiled
-void k4_variant(int v) { g_k4_variant = v; }
 
 // Rows per workgroup: enough workgroups to fill the chip (groups x splits >= ~512: two per CU, each wave with (QG + 1) U NT loads
 // in flight; ~1024 with one block per workgroup row) without making the stack of partial planes (4 per workgroup) taller than it
 // has to be.
 int gram_rows(uint64_t N_pad, int nq, int b)
 {
-   const int QG = g_k4_variant ? gram_group(b) : 1;
+   const int QG = gram_group(b);
    const uint64_t groups = (uint64_t)((nq > 0 ? nq : 1) + QG - 1) / QG, want = QG > 1 ? 512 : 1024;
    uint64_t rows = 8192;
    while (rows > 256 && (N_pad + rows - 1) / rows * groups < want) rows /= 2;
@@ -1320,7 +1318,7 @@ void gram(const double *const *blocks, int nq, const double *W, double *part, ui
 {
    if (nq <= 0) return;
    if (N_pad % 16) throw Error(-1, "gram: the block height must be a multiple of 16 rows");
-   const int QG = g_k4_variant ? gram_group(b) : 1;
+   const int QG = gram_group(b);
    if (QG > 1) {
       dim3 grid((unsigned)gram_splits(N_pad, rows), (unsigned)((nq + QG - 1) / QG));
       if (b == 16)
@@ -1332,8 +1330,6 @@ void gram(const double *const *blocks, int nq, const double *W, double *part, ui
    }
    dim3 grid((unsigned)gram_splits(N_pad, rows), (unsigned)nq); // (`rows` only sets the number of workgroups: 4 partial planes each)
    switch (b) {
-   case 16: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gram<1>), grid, dim3(256), 0, stream, blocks, W, part, N_pad, rows, nq); break;
-   case 32: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gram<2>), grid, dim3(256), 0, stream, blocks, W, part, N_pad, rows, nq); break;
    case 48: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gram<3>), grid, dim3(256), 0, stream, blocks, W, part, N_pad, rows, nq); break;
    case 64: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gram<4>), grid, dim3(256), 0, stream, blocks, W, part, N_pad, rows, nq); break;
    default: throw Error(-1, "gram: block width must be 16, 32, 48 or 64");
@@ -1509,14 +1505,14 @@ __global__ __launch_bounds__(256) void k_block_gemm_lds(const double *const *__r
 constexpr int BG_TPW = 4; // row tiles per wave of k_block_gemm_lds
 int block_gemm_gram_planes(uint64_t N_pad, int b)
 {
-   return (g_k4_variant && (b == 16 || b == 32) && N_pad >= 64) ? (int)((N_pad / 16 + 4 * BG_TPW - 1) / (4 * BG_TPW)) : 0;
+   return ((b == 16 || b == 32) && N_pad >= 64) ? (int)((N_pad / 16 + 4 * BG_TPW - 1) / (4 * BG_TPW)) : 0;
 }
 
 void block_gemm(const double *const *blocks, int nq, const double *C, const double *Init, double *Out, uint64_t N_pad,
                 int b, hipStream_t stream, double *gram_part)
 {
    if (gram_part && !block_gemm_gram_planes(N_pad, b)) throw Error(-1, "block_gemm: no fused Gram for this shape");
-   if (g_k4_variant && (b == 16 || b == 32) && N_pad >= 64) {
+   if ((b == 16 || b == 32) && N_pad >= 64) {
       constexpr int TPW = BG_TPW;
       dim3 grid((unsigned)((N_pad / 16 + 4 * TPW - 1) / (4 * TPW)));
       if (b == 16) {
@@ -1652,7 +1648,7 @@ __global__ __launch_bounds__(256) void k_update_gram16(const double *const *__re
 // workgroups of the fused launch = partial planes it leaves (0: no fused kernel for this shape)
 int update_gram_planes(uint64_t N_pad, int nq, int b)
 {
-   if (!g_k4_variant || b != 16 || nq < 1 || nq > 28 || N_pad < 16 * 512 || FPCA_TEST_ENV("FPCA_K4_NO_FUSED")) return 0;
+   if (b != 16 || nq < 1 || nq > 28 || N_pad < 16 * 512 || FPCA_TEST_ENV("FPCA_K4_NO_FUSED")) return 0;
    return 512;
 }
 
@@ -2001,216 +1997,6 @@ double mfma_peak_tflops(int waves_per_simd, int iters, int pattern, hipStream_t 
    (void)hipFree(d);
    const double flops = (double)blocks * 4 /*waves*/ * (double)iters * 8 * 2048.0;
    return flops / (ms * 1e-3) / 1e12;
-}
-
-// The same for the other matrix instructions the FP kernels could run on, with compiler-scheduled intrinsics (8 independent
-// accumulators, 4 A x 2 B operands in GEMM order, no memory traffic): KIND 0 v_mfma_f32_16x16x4_f32, 1 v_mfma_f32_32x32x2_f32,
-// 2 v_mfma_f64_16x16x4_f64.  fill = 0: zero operands (the issue-limited ceiling); else pseudo-random operands in (-1, 1) -- the
-// multipliers toggle like the real kernels' and the package power cap decides (round 6: the ceiling `fp32_frac` is read against).
-typedef float v16f __attribute__((ext_vector_type(16)));
-template <int KIND>
-__global__ __launch_bounds__(256, 1) void k_mfma_fp_peak(float *out, int iters, uint32_t fill)
-{
-   uint32_t h = (threadIdx.x + 1u) * 2654435761u ^ fill;
-   auto rnd = [&]() {
-      h = h * 1664525u + 1013904223u;
-      return fill ? (float)(int)(h >> 8) * (1.0f / 8388608.0f) - 1.0f : 0.0f;
-   };
-   if constexpr (KIND == 0) {
-      float a[4], b[2];
-      for (float &x : a) x = rnd();
-      for (float &x : b) x = rnd();
-      f4 acc[4][2];
-      for (auto &r : acc)
-         for (auto &x : r) x = (f4){0, 0, 0, 0};
-      for (int it = 0; it < iters; it++) {
-#pragma unroll
-         for (int i = 0; i < 4; i++)
-#pragma unroll
-            for (int j = 0; j < 2; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
-      }
-      float sum = 0;
-      for (auto &r : acc)
-         for (auto &x : r) sum += x[0] + x[1] + x[2] + x[3];
-      if (iters < 0) out[threadIdx.x] = sum;
-   } else if constexpr (KIND == 1) {
-      float a[2], b[2];
-      for (float &x : a) x = rnd();
-      for (float &x : b) x = rnd();
-      v16f acc[2][2];
-      for (auto &r : acc)
-         for (auto &x : r)
-            for (int q = 0; q < 16; q++) x[q] = 0;
-      for (int it = 0; it < iters; it++) {
-#pragma unroll
-         for (int rep = 0; rep < 2; rep++)
-#pragma unroll
-            for (int i = 0; i < 2; i++)
-#pragma unroll
-               for (int j = 0; j < 2; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
-      }
-      float sum = 0;
-      for (auto &r : acc)
-         for (auto &x : r)
-            for (int q = 0; q < 16; q++) sum += x[q];
-      if (iters < 0) out[threadIdx.x] = sum;
-   } else {
-      double a[4], b[2];
-      for (double &x : a) x = rnd();
-      for (double &x : b) x = rnd();
-      d4 acc[4][2];
-      for (auto &r : acc)
-         for (auto &x : r) x = (d4){0, 0, 0, 0};
-      for (int it = 0; it < iters; it++) {
-#pragma unroll
-         for (int i = 0; i < 4; i++)
-#pragma unroll
-            for (int j = 0; j < 2; j++) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
-      }
-      double sum = 0;
-      for (auto &r : acc)
-         for (auto &x : r) sum += x[0] + x[1] + x[2] + x[3];
-      if (iters < 0) out[threadIdx.x] = (float)sum;
-   }
-}
-
-// How much matrix-pipe time do plain VALU instructions cost?  8 independent v_mfma_f32_16x16x4_f32 (32 cycles each) per iteration with
-// VPM independent v_add_u32 per MFMA, either interleaved (one MFMA, VPM adds, ...) or in bursts (8 MFMAs, then 8 VPM adds: the shape
-// of the GEMM kernels' software-pipelined steps).  LDSR > 0: additionally LDSR conflict-free ds_read_b64 per MFMA whose results are
-// waited for one iteration later.  Returns the MFMA rate in TFLOP/s (scripts/mfma_valu_mix.py).
-template <int VPM, bool BURST, int LDSR>
-__global__ __launch_bounds__(256, 1) void k_mfma_valu_mix(float *out, int iters)
-{
-   __shared__ float lds[4096];
-   for (int i = threadIdx.x; i < 4096; i += 256) lds[i] = 0.f;
-   __syncthreads();
-   float a[4], b[2];
-   for (int i = 0; i < 4; i++) a[i] = 1.0f + i + threadIdx.x * 1e-3f;
-   for (int i = 0; i < 2; i++) b[i] = 0.5f + i;
-   f4 acc[8];
-   for (auto &x : acc) x = (f4){0, 0, 0, 0};
-   uint32_t v[8] = {1, 2, 3, 4, 5, 6, 7, 8};
-   f2 ld[8];
-   for (auto &x : ld) x = (f2){0, 0};
-   const uint32_t laddr = (uint32_t)(size_t)(__attribute__((address_space(3))) float *)lds + (threadIdx.x & 63) * 8;
-   for (int it = 0; it < iters; it++) {
-      if constexpr (BURST) {
-#pragma unroll
-         for (int i = 0; i < 8; i++) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i & 3] + ld[i].x, b[i >> 2], acc[i], 0, 0, 0);
-         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-         for (int i = 0; i < 8 * LDSR; i++) asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(ld[i & 7]) : "v"(laddr), "n"((i & 7) * 512));
-#pragma unroll
-         for (int i = 0; i < 8 * VPM; i++) asm volatile("v_add_u32 %0, %0, %1" : "+v"(v[i & 7]) : "v"(v[(i + 1) & 7]));
-         if constexpr (LDSR > 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-         __builtin_amdgcn_sched_barrier(0);
-      } else {
-#pragma unroll
-         for (int i = 0; i < 8; i++) {
-            acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i & 3] + ld[i].x, b[i >> 2], acc[i], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int r = 0; r < LDSR; r++) asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(ld[(i + 4) & 7]) : "v"(laddr), "n"(((i + 4) & 7) * 512));
-#pragma unroll
-            for (int j = 0; j < VPM; j++) asm volatile("v_add_u32 %0, %0, %1" : "+v"(v[(i + j) & 7]) : "v"(v[(i + j + 1) & 7]));
-            if constexpr (LDSR > 0) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(LDSR * 3) : "memory");
-            __builtin_amdgcn_sched_barrier(0);
-         }
-      }
-   }
-   float sum = 0;
-   for (auto &x : acc) sum += x[0] + x[1] + x[2] + x[3];
-   for (auto x : v) sum += (float)x;
-   if (iters < 0) out[threadIdx.x] = sum;
-}
-
-double mfma_valu_mix_tflops(int vpm, bool burst, int ldsr, int waves_per_simd, int iters, hipStream_t stream)
-{
-   float *d = nullptr;
-   if (hipMalloc(&d, 1024) != hipSuccess) throw Error(-3, "hipMalloc failed");
-   const int blocks = 256 * waves_per_simd;
-   hipEvent_t e0, e1;
-   (void)hipEventCreate(&e0);
-   (void)hipEventCreate(&e1);
-   auto go = [&](int n) {
-#define FPCA_MIX(V_, B_, L_)                                                                                  \
-   if (vpm == V_ && burst == B_ && ldsr == L_) {                                                             \
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mfma_valu_mix<V_, B_, L_>), dim3(blocks), dim3(256), 0, stream, d, n); \
-      return;                                                                                                \
-   }
-      FPCA_MIX(0, false, 0) FPCA_MIX(1, false, 0) FPCA_MIX(2, false, 0) FPCA_MIX(3, false, 0) FPCA_MIX(4, false, 0) FPCA_MIX(6, false, 0) FPCA_MIX(8, false, 0)
-      FPCA_MIX(1, true, 0) FPCA_MIX(2, true, 0) FPCA_MIX(3, true, 0) FPCA_MIX(4, true, 0) FPCA_MIX(6, true, 0) FPCA_MIX(8, true, 0)
-      FPCA_MIX(0, false, 1) FPCA_MIX(2, false, 1) FPCA_MIX(3, false, 1) FPCA_MIX(0, true, 1) FPCA_MIX(2, true, 1) FPCA_MIX(3, true, 1)
-#undef FPCA_MIX
-      throw Error(-1, "mfma_valu_mix: variant not instantiated");
-   };
-   go(iters / 10);
-   (void)hipEventRecord(e0, stream);
-   go(iters);
-   (void)hipEventRecord(e1, stream);
-   (void)hipEventSynchronize(e1);
-   float ms = 0;
-   (void)hipEventElapsedTime(&ms, e0, e1);
-   (void)hipEventDestroy(e0);
-   (void)hipEventDestroy(e1);
-   (void)hipFree(d);
-   return (double)blocks * 4 * (double)iters * 8 * 2048.0 / (ms * 1e-3) / 1e12;
-}
-
-double mfma_fp_peak_tflops(int kind, int waves_per_simd, int iters, uint32_t fill, hipStream_t stream)
-{
-   float *d = nullptr;
-   if (hipMalloc(&d, 1024) != hipSuccess) throw Error(-3, "hipMalloc failed");
-   const int blocks = 256 * waves_per_simd;
-   hipEvent_t e0, e1;
-   (void)hipEventCreate(&e0);
-   (void)hipEventCreate(&e1);
-   auto go = [&](int n) {
-      if (kind == 0)
-         hipLaunchKernelGGL(k_mfma_fp_peak<0>, dim3(blocks), dim3(256), 0, stream, d, n, fill);
-      else if (kind == 1)
-         hipLaunchKernelGGL(k_mfma_fp_peak<1>, dim3(blocks), dim3(256), 0, stream, d, n, fill);
-      else
-         hipLaunchKernelGGL(k_mfma_fp_peak<2>, dim3(blocks), dim3(256), 0, stream, d, n, fill);
-   };
-   go(iters / 10);
-   (void)hipEventRecord(e0, stream);
-   go(iters);
-   (void)hipEventRecord(e1, stream);
-   (void)hipEventSynchronize(e1);
-   float ms = 0;
-   (void)hipEventElapsedTime(&ms, e0, e1);
-   (void)hipEventDestroy(e0);
-   (void)hipEventDestroy(e1);
-   (void)hipFree(d);
-   const double flops = (double)blocks * 4 * (double)iters * 8 * (kind == 1 ? 4096.0 : 2048.0);
-   return flops / (ms * 1e-3) / 1e12;
-}
-
-// ------------------------------------------------------------------------------------------------
-// diagnostic: where does the dispatcher place the workgroups of a chip-sized grid?  Every workgroup records its
-// hardware ids and then spins so that the whole grid is co-resident.  (Measured: 256/512/768/1024 workgroups of 256
-// threads land exactly 1/2/3/4 per CU, 32/64/96/128 per XCD.)
-__global__ __launch_bounds__(256, 2) void k_census(uint32_t *out, long long spin)
-{
-   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-   if (threadIdx.x == 0) {
-      const uint32_t hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_REG_HW_ID
-      const uint32_t xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20); // HW_REG_XCC_ID
-      out[blockIdx.x * 2] = hw;
-      out[blockIdx.x * 2 + 1] = xcc;
-      smem_raw[0] = (unsigned char)hw;
-   }
-   const long long t0 = clock64();
-   while (clock64() - t0 < spin) {
-   }
-}
-
-void census(uint32_t *d_out, int nwg, size_t lds_bytes, long long spin, hipStream_t stream)
-{
-   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_census), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-   hipLaunchKernelGGL(k_census, dim3(nwg), dim3(256), lds_bytes, stream, d_out, spin);
-   HIP_CHECK_LAUNCH();
 }
 
 } // namespace kern

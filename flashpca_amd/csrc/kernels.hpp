@@ -52,7 +52,6 @@ void x_t_dense(const double *Xd, const double *T, double *Ypart, uint64_t N_pad,
 // rows) workgroups of `rows` = gram_rows(N_pad, nq, b) rows each); `blocks` = device array of nq pointers
 void gram(const double *const *blocks, int nq, const double *W, double *part, uint64_t N_pad, int b, int rows, hipStream_t stream);
 int gram_rows(uint64_t N_pad, int nq, int b);
-void k4_variant(int v); // lab switch (fpca_debug_k4_variant): 0 = round 4's K4 kernels, 1 = the tiled ones (default)
 int gram_splits(uint64_t N_pad, int rows);
 // Out = (Init ? Init : 0) + sum_q A_q C_q,   C: [nq][b][b] row-major (C_q[p][c]); Out may alias Init or any A_q
 // gram_part non-null (only where block_gemm_gram_planes(N_pad, b) > 0): the launch also leaves that many partial planes [b][b] of
@@ -93,8 +92,6 @@ void mfma_layout_probe(const double *A, const double *B, double *D, hipStream_t 
 
 // issue-rate ceiling of the FP64 MFMA (TFLOP/s) with `waves_per_simd` resident waves per SIMD
 double mfma_peak_tflops(int waves_per_simd, int iters, int pattern, hipStream_t stream);
-// diagnostic: hardware placement (HW_ID, XCC_ID per workgroup) of an nwg-workgroup grid with lds_bytes of LDS each
-void census(uint32_t *d_out, int nwg, size_t lds_bytes, long long spin, hipStream_t stream);
 
 // ---- exact-integer int8-sliced path (kernels_i8.hip) ----
 // one int8 operand cut from an fp64 matrix V[rows_pad][b]: Q[S*b][rows_pad] digits of V * rowscale[row], weights colw,
@@ -150,9 +147,6 @@ void i8_rowscales(const double *mean, const double *sd, uint64_t P_g, uint64_t P
 void transpose_packed(const uint8_t *in, size_t pitch_in, uint64_t N_pad, uint64_t P_pad, uint8_t *out, size_t pitch_out,
                       hipStream_t stream);
 double mfma_i8_peak_tops(int waves_per_simd, int iters, uint32_t fill, hipStream_t stream);
-double mfma_valu_mix_tflops(int vpm, bool burst, int ldsr, int waves_per_simd, int iters, hipStream_t stream);
-double mfma_fp_peak_tflops(int kind, int waves_per_simd, int iters, uint32_t fill, hipStream_t stream); // 0 f32 16x16x4, 1 f32 32x32x2, 2 f64 16x16x4
-double mfma_i8_mix_tops(int mix, int iters, hipStream_t stream);
 void mfma_i8_probe(const int8_t *A, const int8_t *Bt, int *D, hipStream_t stream);
 
 } // namespace kern

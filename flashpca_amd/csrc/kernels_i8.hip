@@ -528,31 +528,26 @@ __device__ __forceinline__ void static_for(F &&f)
 //                 multiplied, M'Q = 1'Q comes from the column sums alone -- half the MFMAs
 enum { I8_FULL = 0, I8_SKIP_EMPTY = 1, I8_NO_MISSING = 2 };
 
-// ABL (builds with -DFPCA_I8_ABLATION only; results are wrong by construction): bit 0 drops the operand staging of the
-// main loop, bit 1 the genotype decode, bit 2 the LDS fragment reads, bit 3 the packed-word loads -- what each costs
-// (scripts/i8_ablation.py); bits 4 / 5 keep every instruction but make the operand stream / the packed words L2-resident
-// (4 chunks re-read): what their misses cost.  Round 2: operand stream 8.68 -> 8.71 ms (nothing), packed words 8.68 ->
-// 8.22 ms -- and that is their HBM energy, not their latency: a variant that issued the packed words 1.5-2.5 chunks ahead
-// instead of half a chunk (chunks in straight-line pairs, four register sets) ran 9.20 ms against 8.70 on the same box.
-// Bit 6 drops the per-chunk barrier: 8.77 -> 8.82 ms, i.e. the barrier and the pipeline refill behind it cost nothing.
-// With an all-zero fp64 operand (same instructions, same traffic; scripts/i8_power_probe.py) the same launch takes 7.07 ms
-// instead of 9.04: the kernel follows the bare MFMA stream's power curve (3470 -> 4540 TOP/s) -- it is energy, not time.
+// What the main loop costs, measured with parts of it compiled out (profiles/r04_i8_ablation_2tile.txt; the 7-tile kernel in
+// docs/history/DESIGN_r04.md §7c): the operand stream's L2 misses cost nothing, the packed words cost their HBM energy rather than
+// their latency (issuing them further ahead ran slower), and at 7 tiles the per-chunk barrier costs nothing.  With an all-zero
+// fp64 operand (same instructions, same traffic) the same launch takes 7.07 ms instead of 9.04: the kernel follows the bare MFMA
+// stream's power curve.
 // HALF: the last of the NT column tiles has only 16 columns (S b = 112 for b = 16, S = 7: 3.5 tiles).  As a 32-wide tile half
 // of it would multiply zero padding -- an eighth of the kernel's MFMA passes; instead the 16 columns run on
 // v_mfma_i32_16x16x64_i8, which takes TWO 32-k steps at once: the genotype fragments of an even and an odd k-step (lanes =
 // 32 rows x 2 k-halves each) are regrouped by v_permlane16_swap into two 16-row x 64-k operands, the slice-column operand is
 // one ds_read_b128 per lane with the matching (k-half, k-step) -> quarter order.  A bare stream of the two mixes
-// (scripts/mfma_mix_probe.py): 3280 -> 3720 useful TOP/s.
-template <bool TWO_, int MT_, int NT_, int WR_, int WC_, int KC_, int G_, int MODE_ = I8_FULL, int ABL_ = 0, bool HALF_ = false>
+// (profiles/r03_mfma_mix_probe.txt): 3280 -> 3720 useful TOP/s.
+template <bool TWO_, int MT_, int NT_, int WR_, int WC_, int KC_, int G_, int MODE_ = I8_FULL, bool HALF_ = false>
 struct I8Cfg {
    static constexpr bool TWO = TWO_, HALF = HALF_;
    static constexpr int MT = MT_, NT = NT_, WR = WR_, WC = WC_, KC = KC_, G = G_, NQ = TWO ? 2 : 1, MODE = MODE_;
-   static constexpr int ABL = ABL_;
    static constexpr int MATS = MODE == I8_NO_MISSING ? 1 : 2;
    static constexpr int NTF = HALF ? NT - 1 : NT;       // full 32-column tiles
    static_assert(!(TWO && MATS == 1), "without E there is only one operand");
    static_assert(WR * WC == 4 && MATS * MT * NT <= 16 && (MT == 1 || G == 1) && G <= NT, "shape");
-   static_assert(!HALF || (WC == 1 && MT == 2 && G == 1 && MODE != I8_SKIP_EMPTY && ABL == 0 && (KC / 32) % 2 == 0), "half-tile variant");
+   static_assert(!HALF || (WC == 1 && MT == 2 && G == 1 && MODE != I8_SKIP_EMPTY && (KC / 32) % 2 == 0), "half-tile variant");
    static constexpr int ROWS = WR * MT * 32;            // workgroup rows
    static constexpr int COLS = WC * NT * 32 - (HALF ? 16 : 0); // workgroup columns of each operand
    static constexpr int LDQ = KC + 16;                  // operand tile row stride (bytes)
@@ -676,12 +671,11 @@ __global__ __launch_bounds__(256, 1) void k_gemm_i8(const uint8_t *__restrict__ 
 
    auto issue_q = [&](auto rr, int cc) {
       constexpr int r = decltype(rr)::value, o = r / NP1, r1 = r % NP1;
-      const int ccq = (C::ABL & 16) ? (cc & 3) : cc; // ablation: the operand stream stays L2-resident (4 chunks, re-read)
-      const int8_t *sb = ((TWO && o) ? Qm : Qg) + (uint64_t)(col0 + C::RSTEP * r1) * k_pad + (uint64_t)ccq * KC;
+      const int8_t *sb = ((TWO && o) ? Qm : Qg) + (uint64_t)(col0 + C::RSTEP * r1) * k_pad + (uint64_t)cc * KC;
       qreg[r] = gload16<0>(sb, qvoff);
    };
    auto issue_p = [&](u4(&dst)[MT][PW], int cc) {
-      const uint8_t *pb = prow + (size_t)((C::ABL & 32) ? (cc & 3) : cc) * (KC / 4); // ablation: packed words L2-resident
+      const uint8_t *pb = prow + (size_t)cc * (KC / 4);
 #pragma unroll
       for (int m = 0; m < MT; m++) {
          dst[m][0] = gload16<0>(pb, pvoff[m]);
@@ -754,11 +748,6 @@ __global__ __launch_bounds__(256, 1) void k_gemm_i8(const uint8_t *__restrict__ 
       read_b(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
       enz[0] = i8_decode<MODE>(pk[0][0][0], ag[0], am[0], tab1);
       wait_b(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
-      if constexpr ((C::ABL & 4) != 0) {
-         read_b(std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
-         wait_b(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
-      }
-      if constexpr ((C::ABL & 2) != 0) enz[1] = i8_decode<MODE>(pk[0][0][1], ag[1], am[1], tab1);
       __builtin_amdgcn_sched_barrier(0);
 
       static_for<NSTEP>([&](auto ss) {
@@ -770,19 +759,19 @@ __global__ __launch_bounds__(256, 1) void k_gemm_i8(const uint8_t *__restrict__ 
          constexpr int ks1 = s1 / (MT * G), m1 = (G == 1) ? s1 % MT : 0, g1 = (G == 1) ? 0 : s1 % G;
          constexpr int bkey1 = ks1 * G + g1, akey1 = ks1 * MT + m1;
          // --- staging of chunk cn: loads in the first half, packed words at the half-way mark, LDS stores in the second
-         if constexpr (s < H && !(C::ABL & 1)) {
+         if constexpr (s < H) {
             static_for<(s + 1) * NP / H - s * NP / H>([&](auto jj) {
                issue_q(std::integral_constant<int, s * NP / H + decltype(jj)::value>{}, cn);
             });
          }
-         if constexpr (s == H - 1 && !(C::ABL & 8)) issue_p(pkn, cn);
-         if constexpr (s >= H && !(C::ABL & 1)) {
+         if constexpr (s == H - 1) issue_p(pkn, cn);
+         if constexpr (s >= H) {
             static_for<(s - H + 1) * NP / H - (s - H) * NP / H>([&](auto jj) {
                store_q(std::integral_constant<int, (s - H) * NP / H + decltype(jj)::value>{}, wst);
             });
          }
          // --- operand fragments of the next micro-step
-         if constexpr (bkey1 != bkey && !(C::ABL & 4))
+         if constexpr (bkey1 != bkey)
             read_b(std::integral_constant<int, ks1>{}, std::integral_constant<int, g1>{}, std::integral_constant<int, (bkey1 & 1)>{});
          // --- this micro-step's MFMAs, the next micro-step's decode in their shadow
          static_for<NG>([&](auto jj) {
@@ -792,7 +781,7 @@ __global__ __launch_bounds__(256, 1) void k_gemm_i8(const uint8_t *__restrict__ 
                if constexpr (MODE == I8_FULL)
                   acc[1][m][n] = __builtin_amdgcn_mfma_i32_32x32x32_i8(am[akey & AMASK], bq[bkey & 1][NQ - 1][j], acc[1][m][n], 0, 0, 0);
             }
-            if constexpr (j == 0 && akey1 != akey && !(C::ABL & 2))
+            if constexpr (j == 0 && akey1 != akey)
                enz[akey1 & AMASK] = i8_decode<MODE>(pk[m1][ks1 >> 2][ks1 & 3], ag[akey1 & AMASK], am[akey1 & AMASK], tab1);
          });
          if constexpr (HALF && (ks & 1) == 1) {
@@ -830,21 +819,19 @@ __global__ __launch_bounds__(256, 1) void k_gemm_i8(const uint8_t *__restrict__ 
             }
          }
          __builtin_amdgcn_sched_barrier(0);
-         if constexpr (bkey1 != bkey && !(C::ABL & 4)) {
+         if constexpr (bkey1 != bkey) {
             wait_b(std::integral_constant<int, g1>{}, std::integral_constant<int, (bkey1 & 1)>{});
             __builtin_amdgcn_sched_barrier(0);
          }
       });
-      if constexpr (!(C::ABL & 8)) {
 #pragma unroll
-         for (int m = 0; m < MT; m++)
+      for (int m = 0; m < MT; m++)
 #pragma unroll
-            for (int h = 0; h < PW; h++) {
-               vm_wait<0>(pkn[m][h]);
-               pk[m][h] = pkn[m][h];
-            }
-      }
-      if constexpr (!(C::ABL & 64)) __syncthreads(); // (ablation bit 6: what the per-chunk barrier + pipeline refill costs)
+         for (int h = 0; h < PW; h++) {
+            vm_wait<0>(pkn[m][h]);
+            pk[m][h] = pkn[m][h];
+         }
+      __syncthreads();
    }
 
    // epilogue: the slices are recombined here, per split and column block, into fp64 partial sums -- virtual column
@@ -995,7 +982,6 @@ __global__ __launch_bounds__(256) void k_i8_combine(const double *__restrict__ p
 struct I8Shape {
    int nt, zb, rows, cols, kc;
    bool half; // the last tile is the 16-column remainder (v_mfma_i32_16x16x64_i8), cols = 32 nt - 16
-   int mt = 2; // 32-row tiles per wave (one-matrix kernel: 2, or 4 for the narrow column blocks)
 };
 
 static I8Shape i8_shape(int S, int b, bool two, int mode = I8_FULL)
@@ -1004,17 +990,12 @@ static I8Shape i8_shape(int S, int b, bool two, int mode = I8_FULL)
    // smallest instantiated block: 2 tiles (few slices of a narrow block: S = 4, b = 16 is 64 slice-columns).  Rounds 2-5 had the
    // two-matrix kernels from 4 (K2) / 3 (K3) tiles up only: the eigensolver's 4-slice passes on data whose missing calls take the dense
    // route multiplied 2 / 1 tiles of zero padding per launch (profiles/r06_missing_routes.txt)
-   int lo = 2;
-   if (FPCA_TEST_ENV("FPCA_I8_LO_R5")) lo = two ? 3 : (mode == I8_NO_MISSING ? 2 : 4); // (A/B against round 5's shapes)
    I8Shape sh;
    sh.zb = (tiles + cap - 1) / cap;
-   sh.nt = std::max(lo, (tiles + sh.zb - 1) / sh.zb);
-   // one matrix only (I8_NO_MISSING): the freed accumulators go into a second row tile per wave (64 rows x NT tiles)
-   sh.rows = (two || mode == I8_NO_MISSING || (sh.nt <= 3 && !FPCA_TEST_ENV("FPCA_I8_LO_R5") && !FPCA_TEST_ENV("FPCA_I8_NARROW_MT1"))) ? 256 : 128;
-   if (!two && mode == I8_NO_MISSING && sh.nt <= 3 && FPCA_TEST_ENV("FPCA_I8_MT4")) { // experiment: 128 rows per wave
-      sh.mt = 4;
-      sh.rows = 512;
-   }
+   sh.nt = std::max(2, (tiles + sh.zb - 1) / sh.zb);
+   // one matrix only (I8_NO_MISSING), or both in a narrow column block: the accumulators fit a second row tile per wave (64 rows x
+   // NT tiles)
+   sh.rows = (two || mode == I8_NO_MISSING || sh.nt <= 3) ? 256 : 128;
    sh.cols = 32 * sh.nt;
    sh.kc = 256;
    // b = 16 with S = 7 slices: 112 slice-columns = 3.5 tiles -- the one-matrix kernel (the default route up to 0.5 % missing
@@ -1082,14 +1063,6 @@ static I8Plan i8_plan(uint64_t rows_pad, uint64_t k_pad, const I8Shape &sh, int 
          }
       }
    }
-   {  // test builds: FPCA_I8_PLAN="nA,s" overrides the decomposition of launches with more than one round of tiles (A/B runs)
-      const char *env_p = FPCA_TEST_ENV("FPCA_I8_PLAN");
-      int e_nA = 0, e_s = 0;
-      if (env_p && std::sscanf(env_p, "%d,%d", &e_nA, &e_s) == 2 && ids >= ncu && e_s >= 1 && e_s * 4 <= chunks) {
-         best_nA = std::min(e_nA / (8 * sh.zb) * (8 * sh.zb), ids);
-         best_s = best_nA == ids ? 1 : e_s;
-      }
-   }
    I8Plan p;
    p.nA = best_nA;
    p.cpsB = (chunks + best_s - 1) / best_s;
@@ -1127,18 +1100,12 @@ template <class C>
 static void launch_i8(const I8Plan &pl, hipStream_t stream, const uint8_t *packed, size_t pitch, const int8_t *Qg, const int8_t *Qm,
                       uint64_t k_pad, const double *wg, const double *wm, int bw, double *ws, uint64_t rows_pad, int chunks_total, int zb, uint32_t tab1)
 {
-   static bool attr_set = false, attr_set2 = false;
+   static bool attr_set = false;
    if (!attr_set) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gemm_i8<C>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
       attr_set = true;
    }
-   // (test builds: FPCA_I8_LDS_PAD = extra bytes of dynamic LDS per workgroup, i.e. fewer co-resident workgroups per CU)
-   static const int lds_pad = FPCA_TEST_ENV("FPCA_I8_LDS_PAD") ? atoi(FPCA_TEST_ENV("FPCA_I8_LDS_PAD")) : 0;
-   if (lds_pad && !attr_set2) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gemm_i8<C>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES + lds_pad);
-      attr_set2 = true;
-   }
-   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gemm_i8<C>), dim3(pl.grid), dim3(256), C::LDS_BYTES + lds_pad, stream, packed, pitch, Qg, Qm, k_pad, wg, wm, bw,
+   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gemm_i8<C>), dim3(pl.grid), dim3(256), C::LDS_BYTES, stream, packed, pitch, Qg, Qm, k_pad, wg, wm, bw,
                       ws, rows_pad, chunks_total, zb, pl.nA, pl.sB, pl.cpsB, pl.rowB0, pl.rowsB, tab1);
 }
 
@@ -1160,94 +1127,49 @@ void gemm_i8(const uint8_t *packed, size_t pitch, const int8_t *Qg, const int8_t
    if (gemm_events) (void)hipEventRecord(gemm_events[0], stream);
    if (two && mode == I8_NO_MISSING) throw Error(-1, "gemm_i8: without missing genotypes both matrices share one operand (pass Qm == Qg)");
 #define FPCA_I8_K3(NT_, MODE_) launch_i8<I8Cfg<true, 2, NT_, 4, 1, 256, 1, MODE_>>(FPCA_I8_ARGS)
-#define FPCA_I8_K2(NT_, MODE_) launch_i8<I8Cfg<false, (MODE_ == I8_NO_MISSING ? 2 : 1), NT_, 4, 1, 256, (MODE_ == I8_NO_MISSING ? 1 : 2), MODE_>>(FPCA_I8_ARGS)
-// (narrow column blocks: 64-row waves for both matrices too -- the accumulators fit, the operand tile is staged for twice the rows)
-#define FPCA_I8_K2W(NT_, MODE_) launch_i8<I8Cfg<false, 2, NT_, 4, 1, 256, 1, MODE_>>(FPCA_I8_ARGS)
-#define FPCA_I8_K2_NT(MODE_)                                                                                 \
-   switch (sh.nt) {                                                                                           \
-   case 2: if (sh.rows == 256) FPCA_I8_K2W(2, MODE_); else FPCA_I8_K2(2, MODE_); break;                       \
-   case 3: if (sh.rows == 256) FPCA_I8_K2W(3, MODE_); else FPCA_I8_K2(3, MODE_); break;                       \
-   case 4: FPCA_I8_K2(4, MODE_); break;                                                                       \
-   case 5: FPCA_I8_K2(5, MODE_); break;                                                                       \
-   case 6: FPCA_I8_K2(6, MODE_); break;                                                                       \
-   case 7: FPCA_I8_K2(7, MODE_); break;                                                                       \
-   default: FPCA_I8_K2(8, MODE_); break;                                                                      \
+// one matrix, or both in a narrow column block (<= 3 tiles): 64-row waves; both from 4 tiles up: 32-row waves, the tiles in 2 groups
+#define FPCA_I8_K2(NT_, MODE_)                                                                                               \
+   launch_i8<I8Cfg<false, (MODE_ == I8_NO_MISSING || NT_ <= 3 ? 2 : 1), NT_, 4, 1, 256, (MODE_ == I8_NO_MISSING || NT_ <= 3 ? 1 : 2), \
+                   MODE_>>(FPCA_I8_ARGS)
+#define FPCA_I8_K3_NT(MODE_)                       \
+   switch (sh.nt) {                                \
+   case 2: FPCA_I8_K3(2, MODE_); break;            \
+   case 3: FPCA_I8_K3(3, MODE_); break;            \
+   default: FPCA_I8_K3(4, MODE_); break;           \
    }
-   if (two && sh.half)
-      launch_i8<I8Cfg<true, 2, 4, 4, 1, 256, 1, I8_FULL, 0, true>>(FPCA_I8_ARGS);
-   else if (!two && sh.half && mode == I8_FULL)
-      launch_i8<I8Cfg<false, 2, 4, 4, 1, 256, 1, I8_FULL, 0, true>>(FPCA_I8_ARGS);
-   else if (two) {
-      if (mode == I8_SKIP_EMPTY) {
-         if (sh.nt == 2)
-            FPCA_I8_K3(2, I8_SKIP_EMPTY);
-         else if (sh.nt == 3)
-            FPCA_I8_K3(3, I8_SKIP_EMPTY);
-         else
-            FPCA_I8_K3(4, I8_SKIP_EMPTY);
-      } else {
-         if (sh.nt == 2)
-            FPCA_I8_K3(2, I8_FULL);
-         else if (sh.nt == 3)
-            FPCA_I8_K3(3, I8_FULL);
-         else
-            FPCA_I8_K3(4, I8_FULL);
-      }
+#define FPCA_I8_K2_NT(MODE_)                       \
+   switch (sh.nt) {                                \
+   case 2: FPCA_I8_K2(2, MODE_); break;            \
+   case 3: FPCA_I8_K2(3, MODE_); break;            \
+   case 4: FPCA_I8_K2(4, MODE_); break;            \
+   case 5: FPCA_I8_K2(5, MODE_); break;            \
+   case 6: FPCA_I8_K2(6, MODE_); break;            \
+   case 7: FPCA_I8_K2(7, MODE_); break;            \
+   default: FPCA_I8_K2(8, MODE_); break;           \
+   }
+   if (two) {
+      if (sh.half)
+         launch_i8<I8Cfg<true, 2, 4, 4, 1, 256, 1, I8_FULL, true>>(FPCA_I8_ARGS);
+      else if (mode == I8_SKIP_EMPTY)
+         FPCA_I8_K3_NT(I8_SKIP_EMPTY)
+      else
+         FPCA_I8_K3_NT(I8_FULL)
    } else if (mode == I8_NO_MISSING) {
-#ifdef FPCA_I8_ABLATION
-      static const char *abl = FPCA_TEST_ENV("FPCA_I8_ABL");
-      const int ab = abl ? atoi(abl) : 0;
-#define FPCA_I8_AB(A_) launch_i8<I8Cfg<false, 2, 7, 4, 1, 256, 1, I8_NO_MISSING, A_>>(FPCA_I8_ARGS)
-      if (ab && sh.nt == 7) {
-         switch (ab) {
-         case 1: FPCA_I8_AB(1); break;
-         case 2: FPCA_I8_AB(2); break;
-         case 4: FPCA_I8_AB(4); break;
-         case 8: FPCA_I8_AB(8); break;
-         case 9: FPCA_I8_AB(9); break;
-         case 6: FPCA_I8_AB(6); break;
-         case 16: FPCA_I8_AB(16); break;
-         case 32: FPCA_I8_AB(32); break;
-         case 48: FPCA_I8_AB(48); break;
-         case 64: FPCA_I8_AB(64); break;
-         case 112: FPCA_I8_AB(112); break;
-         default: FPCA_I8_AB(15); break;
-         }
-      } else if (ab && sh.nt == 2 && sh.mt == 2) { // the 2-tile kernel of the 4-slice passes (profiles/r04_i8_ablation_2tile.txt)
-#define FPCA_I8_AB2(A_) launch_i8<I8Cfg<false, 2, 2, 4, 1, 256, 1, I8_NO_MISSING, A_>>(FPCA_I8_ARGS)
-         switch (ab) {
-         case 1: FPCA_I8_AB2(1); break;
-         case 2: FPCA_I8_AB2(2); break;
-         case 8: FPCA_I8_AB2(8); break;
-         case 16: FPCA_I8_AB2(16); break;
-         case 32: FPCA_I8_AB2(32); break;
-         case 48: FPCA_I8_AB2(48); break;
-         case 64: FPCA_I8_AB2(64); break;
-         default: FPCA_I8_AB2(15); break;
-         }
-      } else
-#endif
       if (sh.half && sh.nt == 2)
-         launch_i8<I8Cfg<false, 2, 2, 4, 1, 256, 1, I8_NO_MISSING, 0, true>>(FPCA_I8_ARGS);
+         launch_i8<I8Cfg<false, 2, 2, 4, 1, 256, 1, I8_NO_MISSING, true>>(FPCA_I8_ARGS);
       else if (sh.half)
-         launch_i8<I8Cfg<false, 2, 4, 4, 1, 256, 1, I8_NO_MISSING, 0, true>>(FPCA_I8_ARGS);
-      else if (sh.nt == 2 && sh.mt == 4)
-         launch_i8<I8Cfg<false, 4, 2, 4, 1, 256, 1, I8_NO_MISSING>>(FPCA_I8_ARGS);
-      else if (sh.nt == 3 && sh.mt == 4)
-         launch_i8<I8Cfg<false, 4, 3, 4, 1, 256, 1, I8_NO_MISSING>>(FPCA_I8_ARGS);
-      else if (sh.nt == 2)
-         launch_i8<I8Cfg<false, 2, 2, 4, 1, 256, 1, I8_NO_MISSING>>(FPCA_I8_ARGS);
-      else if (sh.nt == 3)
-         launch_i8<I8Cfg<false, 2, 3, 4, 1, 256, 1, I8_NO_MISSING>>(FPCA_I8_ARGS);
+         launch_i8<I8Cfg<false, 2, 4, 4, 1, 256, 1, I8_NO_MISSING, true>>(FPCA_I8_ARGS);
       else
          FPCA_I8_K2_NT(I8_NO_MISSING)
    } else if (mode == I8_SKIP_EMPTY) {
       FPCA_I8_K2_NT(I8_SKIP_EMPTY)
+   } else if (sh.half) {
+      launch_i8<I8Cfg<false, 2, 4, 4, 1, 256, 1, I8_FULL, true>>(FPCA_I8_ARGS);
    } else {
       FPCA_I8_K2_NT(I8_FULL)
    }
 #undef FPCA_I8_K2_NT
-#undef FPCA_I8_K2W
+#undef FPCA_I8_K3_NT
 #undef FPCA_I8_K2
 #undef FPCA_I8_K3
 #undef FPCA_I8_ARGS
@@ -1899,75 +1821,6 @@ __global__ __launch_bounds__(256, 1) void k_mfma_i8_peak(int *out, int iters, ui
    int r;
    asm volatile("s_nop 7\n\ts_nop 7\n\tv_mov_b32 %0, v0" : "=v"(r)::"v0", "v1", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9", "v10", "v11", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19", "v20", "v21", "v22", "v23", "v24", "v25", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", "v34", "v35", "v36", "v37", "v38", "v39", "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63", "v64", "v65", "v66", "v67", "v68", "v69", "v70", "v71", "v72", "v73", "v74", "v75", "v76", "v77", "v78", "v79", "v80", "v81", "v82", "v83", "v84", "v85", "v86", "v87", "v88", "v89", "v90", "v91", "v92", "v93", "v94", "v95", "v96", "v97", "v98", "v99", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112", "v113", "v114", "v115", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127", "v128", "v129", "v130", "v131", "v132", "v133", "v134", "v135", "v136", "v137", "v138", "v139", "v140", "v141", "v142", "v143");
    if (r == 0x7fffffff) out[threadIdx.x] = r;
-}
-
-// diagnostic: what the 16-column remainder of the b = 16 GEMM costs on the matrix pipe.  One loop iteration = the MFMAs of a
-// wave (64 rows) for two 32-k steps against S b = 112 slice-columns, random operands:
-//   MIX = 0: 16 x v_mfma_i32_32x32x32_i8 (4 column tiles; in the 4th, columns 16..31 of the operand are zero padding)
-//   MIX = 1: 12 x 32x32x32 (3 full tiles) + 4 x v_mfma_i32_16x16x64_i8 (the 16 remaining columns, both k-steps at once)
-// Returns useful TOP/s (2 x 64 x 112 x 64 operations per iteration).
-template <int MIX>
-__global__ __launch_bounds__(256, 1) void k_mfma_i8_mix(int *out, int iters, uint32_t seed)
-{
-   const uint32_t l = threadIdx.x & 63;
-   v4i a[4], b[4], bh[4];
-   for (int t = 0; t < 4; t++)
-      for (int q = 0; q < 4; q++) {
-         uint32_t h = (seed + 0x9E3779B9u * (t * 4 + q + 1)) ^ (l * 0x85EBCA6Bu);
-         h ^= h >> 15;
-         h *= 0x2C1B3C6Du;
-         h ^= h >> 12;
-         a[t][q] = (int)(h & 0x02020202u) | (int)((h >> 8) & 0x01010101u); // genotype-like bytes 0..3
-         b[t][q] = (int)(h * 0x9E3779B1u);                                // full-range bytes
-         bh[t][q] = ((l & 31) >= 16) ? 0 : b[t][q];                       // a column tile whose upper 16 columns are padding
-      }
-   v16i acc[16];
-   v4i acch[4];
-   for (int t = 0; t < 16; t++)
-      for (int r = 0; r < 16; r++) acc[t][r] = 0;
-   for (int t = 0; t < 4; t++) acch[t] = (v4i){0, 0, 0, 0};
-   for (int it = 0; it < iters; it++) {
-      if (MIX == 0) {
-#pragma unroll
-         for (int t = 0; t < 16; t++) acc[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[t & 3], (t & 3) == 3 ? bh[t >> 2] : b[t & 3], acc[t], 0, 0, 0);
-      } else {
-#pragma unroll
-         for (int t = 0; t < 12; t++) acc[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[t & 3], b[t % 3], acc[t], 0, 0, 0);
-#pragma unroll
-         for (int t = 0; t < 4; t++) acch[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[t], b[t], acch[t], 0, 0, 0);
-      }
-      asm volatile("" ::: "memory");
-   }
-   int r = 0;
-   for (int t = 0; t < 16; t++) r ^= acc[t][t & 15];
-   for (int t = 0; t < 4; t++) r ^= acch[t][t];
-   if (r == 0x7fffffff) out[threadIdx.x] = r;
-}
-
-double mfma_i8_mix_tops(int mix, int iters, hipStream_t stream)
-{
-   int *d = nullptr;
-   (void)hipMalloc(&d, 4096);
-   hipEvent_t e0, e1;
-   (void)hipEventCreate(&e0);
-   (void)hipEventCreate(&e1);
-   auto go = [&](int n) {
-      if (mix)
-         hipLaunchKernelGGL(k_mfma_i8_mix<1>, dim3(256), dim3(256), 0, stream, d, n, 0x1234567u);
-      else
-         hipLaunchKernelGGL(k_mfma_i8_mix<0>, dim3(256), dim3(256), 0, stream, d, n, 0x1234567u);
-   };
-   go(iters / 10);
-   (void)hipEventRecord(e0, stream);
-   go(iters);
-   (void)hipEventRecord(e1, stream);
-   (void)hipEventSynchronize(e1);
-   float ms = 0;
-   (void)hipEventElapsedTime(&ms, e0, e1);
-   (void)hipEventDestroy(e0);
-   (void)hipEventDestroy(e1);
-   (void)hipFree(d);
-   return 256.0 * 4 * (double)iters * 2.0 * 64 * 112 * 64 / (ms * 1e-3) / 1e12;
 }
 
 double mfma_i8_peak_tops(int waves_per_simd, int iters, uint32_t fill, hipStream_t stream)

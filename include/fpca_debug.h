@@ -50,9 +50,7 @@ int fpca_debug_mfma_i8_probe(const int8_t *A, const int8_t *Bt, int32_t *D);
 /* diagnostic: sustained rate (TFLOP/s) of a pure v_mfma_f64_16x16x4_f64 stream with `waves_per_simd` (1..8) resident
  * waves per SIMD and no memory traffic; pattern 0..3 selects the operand-register sharing pattern (kernels.hip).  The
  * practical ceiling to read the GEMM kernels' roofline fraction against (72-74 TFLOP/s at 2 waves/SIMD vs 78.6 datasheet).
- * pattern 10 / 11: v_mfma_i32_32x32x32_i8 in TOP/s with zero / pseudo-random operands.
- * pattern 20 / 21: v_mfma_f32_16x16x4_f32, 22 / 23: v_mfma_f32_32x32x2_f32, 24 / 25: v_mfma_f64_16x16x4_f64 -- zero / pseudo-random
- * operands (compiler-scheduled intrinsics): with random operands the package power cap sets the ceiling. */
+ * pattern 10 / 11: v_mfma_i32_32x32x32_i8 in TOP/s with zero / pseudo-random operands.  Any other pattern: FPCA_EINVAL. */
 int fpca_debug_mfma_peak(int waves_per_simd, int iters, int pattern, double *tflops);
 /* diagnostic (tests/test_gpu_kernels.py): the K4 helpers the eigensolver runs on its HBM-resident basis, on caller data and
  * through the very backend object the solver drives (HipBackend::gram incl. its split-K plane reduction, HipBackend::gemm).
@@ -62,21 +60,14 @@ int fpca_debug_mfma_peak(int waves_per_simd, int iters, int pattern, double *tfl
  *   G_out (may be NULL): [p][c] = sum_s Out[s][p] Out[s][c], from the SAME launch that writes Out (HipBackend::gemm_gram)  b b doubles */
 int fpca_debug_k4(fpca_ctx *ctx, int b, int nq, const double *V, const double *W, double *C_gram, const double *C_in, int use_init,
                   double *Out, double *G_out);
-/* lab (process-wide A/B switches, 1 = default = the round-5 kernels, 0 = the kernels of rounds 1-4):
- *   which 0: the K4 kernels of the eigensolver's orthogonalisation -- Gram with one W tile per 8 basis blocks, block GEMM with its
- *            coefficients in LDS and four row tiles per wave.
- * fpca_debug_k4_bench: launch times of the K4 kernels on nq device-resident random basis blocks of this context's height: ms per
- * Gram (kernel + plane reduction) and per block GEMM (Out = Init + sum_q V_q C_q) */
-int fpca_debug_variant(int which, int variant);
 /* round 6: the first Gram-Schmidt projection's update and the second projection's Gram matrices from ONE pass over the basis
  * (HipBackend::gemm_gramvw, k_update_gram16): Out (may be NULL) = W + sum_q V_q C_in[q]; Cg: [q][p][c] = sum_s V_q[s][p] Out[s][c] for
  * q < nq, Cg[nq] = Out' Out -- (nq + 1) b b doubles; and its launch time (kernel + plane reduction) on nq random blocks */
 int fpca_debug_k4_fused(fpca_ctx *ctx, int b, int nq, const double *V, const double *W, const double *C_in, double *Out, double *Cg);
 int fpca_debug_k4_fused_bench(fpca_ctx *ctx, int b, int nq, int reps, double *ms_fused);
+/* launch times of the K4 kernels on nq device-resident random basis blocks of this context's height: ms per Gram (kernel + plane
+ * reduction) and per block GEMM (Out = Init + sum_q V_q C_q) */
 int fpca_debug_k4_bench(fpca_ctx *ctx, int b, int nq, int reps, double *ms_gram, double *ms_gemm);
-/* diagnostic: placement census of an nwg-workgroup grid (256 threads, lds_bytes dynamic LDS each): out[2i] = HW_ID,
- * out[2i+1] = XCC_ID of workgroup i */
-int fpca_debug_census(int nwg, uint64_t lds_bytes, uint32_t *out);
 
 #ifdef __cplusplus
 }

@@ -43,7 +43,7 @@ timeout -k 10 900 python bench.py --full --workload cfg5 $Q --no-e2e > $O/bench_
 timeout -k 10 900 python bench.py --full --blockvec 32 $Q --no-e2e --no-alt > $O/bench_cfg3_n1_b32.json 2>/dev/null
 timeout -k 10 900 python scripts/ortho_slice_cost.py > $O/ortho_slice_cost.txt 2>&1
 timeout -k 10 900 python scripts/partial_download_probe.py > $O/partial_download.txt 2>&1
-timeout -k 10 900 python scripts/solve_profiles.py 1 2 > $O/solve_profiles.txt 2>&1
+timeout -k 10 900 python scripts/solve_profiles.py 2 > $O/solve_profiles.txt 2>&1
 timeout -k 10 900 python scripts/k4_bench.py > $O/k4_bench.txt 2>&1
 timeout -k 10 900 python scripts/fp_apply_bench.py > $O/fp_apply_bench.txt 2>&1
 timeout -k 10 900 python scripts/missing_routes_probe.py > $O/missing_routes.txt 2>&1
