@@ -134,6 +134,7 @@ SIGNATURES = {
     "fpca_pca_row_ranges": (_I, [_P, C.POINTER(PcaOpts), C.POINTER(_U64), _I]),
     "fpca_pca": (_I, [_P, C.POINTER(PcaOpts), _P, _P, _P, _P, _P, _P, C.POINTER(PcaInfo)]),
     "fpca_check": (_I, [_P, _P, C.c_int64, _P, _I, _I, _P, C.POINTER(_D), C.POINTER(_D)]),
+    "fpca_ucca": (_I, [_P, _P, C.c_int64, _I, _I, _P, C.c_int64]),
     "fpca_bench_apply": (_I, [_P, _I, _I, _I, C.POINTER(BenchResult)]),
     "fpca_profile_begin": (_I, [_P, _I]),
     "fpca_profile_sample_every": (_I, [_P, _I]),
@@ -146,6 +147,7 @@ SIGNATURES = {
     "fpca_debug_k4_bench": (_I, [_P, _I, _I, _I, C.POINTER(_D), C.POINTER(_D)]),
     "fpca_debug_k4_fused": (_I, [_P, _I, _I, _P, _P, _P, _P, _P]),
     "fpca_debug_k4_fused_bench": (_I, [_P, _I, _I, _I, C.POINTER(_D)]),
+    "fpca_debug_f_sf": (_I, [_D, _U64, _I, C.POINTER(_D), C.POINTER(_D)]),
 }
 
 ABI_VERSION = 4  # FPCA_ABI_VERSION of the include/fpca.h the structures above mirror

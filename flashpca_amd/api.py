@@ -230,6 +230,20 @@ class Context:
         check(lib().fpca_check(self.h, _p(evec), evec.shape[0], _p(evals), k, DIVISOR[div], _p(err), C.byref(mse), C.byref(rmse)))
         return err, mse.value, rmse.value
 
+    def ucca(self, Y, standy="sd"):
+        """fpca_ucca: per-SNP association of this shard's SNPs with the N x k phenotypes Y (NaN = missing), standardised by `standy`
+        (none / sd / binom / binom2 / center).  Returns a (P, 3) array: R, Fstat, P (RandomPCA::ucca + wilks, randompca.cpp:103-119,
+        530-625)."""
+        if standy not in _lib.STANDARDISE_DENSE:
+            raise ValueError("standy must be one of %s" % sorted(_lib.STANDARDISE_DENSE))
+        Y = np.asarray(Y, dtype=np.float64)
+        Y = np.asfortranarray(Y.reshape(-1, 1) if Y.ndim == 1 else Y)
+        if Y.ndim != 2 or Y.shape[0] != self.N:
+            raise ValueError("Y must have %d rows (one per sample), it has %d" % (self.N, Y.shape[0]))
+        res = np.empty((self.P, 3), order="F")
+        check(lib().fpca_ucca(self.h, _p(Y), Y.shape[0], Y.shape[1], _lib.STANDARDISE_DENSE[standy], _p(res), self.P))
+        return res
+
     # ---- measurement -----------------------------------------------------------------------------------
     def bench_apply(self, b=32, steps=10, warmup=2):
         r = BenchResult()
@@ -292,6 +306,84 @@ def flashpca(X, ndim=10, stand="binom2", divisor="p", maxiter=500, tol=1e-6, do_
         res["center"] = r["meansd"][:, 0]
         res["scale"] = r["meansd"][:, 1]
     return res
+
+
+_STAND_ORDER = ("binom2", "binom", "sd", "center", "none")  # R: match.arg's choices, first = default
+
+
+def _match_arg(name, value):
+    if value not in _STAND_ORDER:
+        raise ValueError("'arg' should be one of %s" % ", ".join('"%s"' % m for m in _STAND_ORDER) + " (%s)" % name)
+    return value
+
+
+def _is_012(A):
+    return bool(np.all(np.isin(A[~np.isnan(A)], (0.0, 1.0, 2.0))))
+
+
+def ucca(X, Y, standx="binom2", standy="binom2", check_geno=True, check_fam=True, verbose=False, device=0):
+    """Per-SNP canonical correlation (ANOVA of all phenotypes on each SNP, plink.multivariate); mirrors ucca() of the reference's R
+    package (flashpcaR/R/ucca.R): same arguments and defaults, its stop() checks raised as ValueError with R's wording.
+
+    X: PLINK root name (X.bed / X.bim / X.fam; standx binom or binom2), or a numeric N x P matrix (NaN = missing; any of the five
+    standardisations).  Y: N x k phenotypes (NaN = missing, mean-imputed).
+    Returns result (P x 3: R, Fstat, P), npheno and, for the PLINK input, snp_ids in .bim order (ucca_plink_internal,
+    flashpcaR/src/flashpca.cpp:275-334).
+    """
+    import warnings
+
+    standx = _match_arg("standx", standx)
+    standy = _match_arg("standy", standy)
+    try:
+        Y = np.asarray(Y, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("Y must be a numeric matrix")
+    if Y.ndim == 1:
+        Y = Y.reshape(-1, 1)  # R: cbind(Y)
+    if Y.ndim != 2:
+        raise ValueError("Y must be a numeric matrix")
+    if np.isnan(Y).any():
+        warnings.warn("Y contains missing values, will be mean-imputed")
+    if isinstance(X, str):
+        if standx not in STANDARDISE:
+            raise ValueError("When using PLINK data, you must use standx='binom' or 'binom2'")
+        n = count_fam_rows(X + ".fam")
+        if check_fam:
+            if Y.shape[1] > n:
+                raise ValueError("The phenotype matrix Y cannot have more columns than the sample size")
+            if Y.shape[0] != n:
+                raise ValueError("The number of rows in %s.fam and Y don't match" % X)
+    else:
+        try:
+            X = np.asarray(X, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("X must be a numeric matrix or a string naming a PLINK fileset")
+        if X.ndim == 1:
+            X = X.reshape(-1, 1)
+        if X.ndim != 2:
+            raise ValueError("X must be a numeric matrix or a string naming a PLINK fileset")
+        if np.isnan(X).any():
+            warnings.warn("X contains missing values, will be mean-imputed")
+        if Y.shape[1] > X.shape[0]:
+            raise ValueError("The phenotype matrix Y cannot have more columns than the sample size")
+        if Y.shape[0] != X.shape[0]:
+            raise ValueError("The number of rows in X and Y don't match")
+        if standx in STANDARDISE and check_geno and not _is_012(X):
+            raise ValueError("Your X matrix contains values other than {0, 1, 2}, standx='binom'/'binom2' can't be used here")
+    if standy in STANDARDISE and check_geno and not _is_012(Y):
+        raise ValueError("Your Y matrix contains values other than {0, 1, 2}, standy='binom'/'binom2' can't be used here")
+    if isinstance(X, str):
+        ctx = Context.from_bed(X + ".bed", n, stand=standx, device=device, accum="auto")
+    else:
+        ctx = Context.from_dense(X, stand=standx, device=device)
+    with ctx:
+        if verbose:
+            print("UCCA online mode, N=%d p=%d" % (ctx.N, ctx.P))
+        res = ctx.ucca(Y, standy=standy)
+    out = dict(result=res, npheno=Y.shape[1])
+    if isinstance(X, str):
+        out["snp_ids"] = _read_bim(X)[0]
+    return out
 
 
 def _read_bim(prefix):

@@ -3,7 +3,8 @@
 // Same flags (flashpca.cpp:41-92), same defaults (ndim 10, standx binom2, div p, tol 1e-6, maxiter 500, precision 7,
 // suffix .txt), same stdout milestones and the same output files/format (eigenvalues / eigenvectors / pcs / pve
 // [/ loadings / meansd], flashpca.cpp:755-878).  Host C++ only: all arithmetic goes through the C ABI of libfpca.so
-// (include/fpca.h); there is no CPU compute path.  Modes outside the PCA hot path (--scca, --ucca) are refused.
+// (include/fpca.h); there is no CPU compute path.  Besides PCA, --check and --project, --ucca (per-SNP association with the
+// --pheno phenotypes, RandomPCA::ucca) runs on one GPU; --scca is refused.
 // New, MI355X-specific flags: --device, --blockvec, --maxblocks, --accum.  --memory/--blocksize/--batch/--numthreads are
 // accepted for compatibility; the packed matrix is always fully resident in HBM so they have no effect.
 #include <cerrno>
@@ -65,7 +66,7 @@ struct OptSpec {
 const OptSpec OPTS[] = {
    {"help", 0, false, "produce help message"},
    {"scca", 0, false, "perform sparse canonical correlation analysis (SCCA) [not supported by this build]"},
-   {"ucca", 0, false, "perform per-SNP canonical correlation analysis [not supported by this build]"},
+   {"ucca", 0, false, "perform per-SNP canonical correlation analysis (UCCA): one F test of all --pheno phenotypes per SNP, written to ucca<suffix>"},
    {"project", 'p', false, "project new samples onto existing principal components"},
    {"batch", 0, false, "load all genotypes into RAM at once (no effect: the packed matrix is always resident in HBM)"},
    {"memory", 'm', true, "size of block, in MB (no effect)"},
@@ -75,11 +76,11 @@ const OptSpec OPTS[] = {
    {"bed", 0, true, "PLINK bed file"},
    {"bim", 0, true, "PLINK bim file"},
    {"fam", 0, true, "PLINK fam file"},
-   {"pheno", 0, true, "PLINK phenotype file"},
+   {"pheno", 0, true, "PLINK phenotype file (UCCA: FID, IID, then one column per phenotype; one row per .fam sample)"},
    {"bfile", 0, true, "PLINK root name"},
    {"ndim", 'd', true, "number of PCs to output"},
    {"standx", 's', true, "standardization method for genotypes [binom2 | binom]"},
-   {"standy", 0, true, "standardization method for phenotypes (CCA only; ignored)"},
+   {"standy", 0, true, "standardization method for phenotypes in UCCA mode [sd | binom2 | binom | none | center] (default sd; ignored by PCA)"},
    {"div", 0, true, "whether to divide the eigenvalues by p, n - 1, or don't divide [p | n1 | none]"},
    {"outpc", 0, true, "PC output file"},
    {"outpcx", 0, true, "X PC output file, for CCA (ignored)"},
@@ -474,7 +475,7 @@ int main(int argc, char *argv[])
    }
 
    // ---- mode selection (flashpca.cpp:136-228) ------------------------------------------------------------
-   enum { MODE_PCA, MODE_CHECK, MODE_PROJECT } mode = MODE_PCA;
+   enum { MODE_PCA, MODE_CHECK, MODE_PROJECT, MODE_UCCA } mode = MODE_PCA;
    const char *modes[] = {"ucca", "scca", "check", "project"};
    for (const char *m1 : modes)
       for (const char *m2 : modes)
@@ -482,11 +483,12 @@ int main(int argc, char *argv[])
             std::cerr << "Error: conflicting modes requested: --" << m1 << ", --" << m2 << std::endl << "Use --help to get more help" << std::endl;
             return EXIT_FAILURE;
          }
-   if (has("scca") || has("ucca")) {
-      std::cerr << "Error: --scca / --ucca are outside the PCA path this build implements" << std::endl;
+   if (has("scca")) {
+      std::cerr << "Error: --scca is outside the PCA path this build implements" << std::endl;
       return EXIT_FAILURE;
    }
-   if (has("check")) mode = MODE_CHECK;
+   if (has("ucca")) mode = MODE_UCCA;
+   else if (has("check")) mode = MODE_CHECK;
    else if (has("project")) {
       mode = MODE_PROJECT;
       if (!has("inload")) {
@@ -530,6 +532,13 @@ int main(int argc, char *argv[])
          std::cerr << "Error: you must specify either --bfile or --bed / --fam / --bim" << std::endl << "Use --help to get more help" << std::endl;
          return EXIT_FAILURE;
       }
+      std::string pheno_file; // flashpca.cpp:316-322
+      if (has("pheno"))
+         pheno_file = vm["pheno"];
+      else if (mode == MODE_UCCA) {
+         std::cerr << "Error: you must specify a phenotype file in CCA/UCCA/SCCA mode using --pheno" << std::endl;
+         return EXIT_FAILURE;
+      }
 
       int n_dim = 10;
       if (has("ndim")) {
@@ -549,6 +558,19 @@ int main(int argc, char *argv[])
             return EXIT_FAILURE;
          }
       }
+      int stand_method_y = FPCA_STANDARDISE_SD; // flashpca.cpp:352-372 (read in UCCA mode only: PCA has no phenotypes)
+      if (mode == MODE_UCCA && has("standy")) {
+         const std::string m = vm["standy"];
+         if (m == "binom") stand_method_y = FPCA_STANDARDISE_BINOM;
+         else if (m == "binom2") stand_method_y = FPCA_STANDARDISE_BINOM2;
+         else if (m == "sd") stand_method_y = FPCA_STANDARDISE_SD;
+         else if (m == "center") stand_method_y = FPCA_STANDARDISE_CENTER;
+         else if (m == "none") stand_method_y = FPCA_STANDARDISE_NONE;
+         else {
+            std::cerr << "Error: unknown standardization method (--standy): " << m << std::endl;
+            return EXIT_FAILURE;
+         }
+      }
       std::string suffix = has("suffix") ? vm["suffix"] : ".txt";
       std::string pcfile = has("outpc") ? vm["outpc"] : "pcs" + suffix;
       std::string eigvecfile = has("outvec") ? vm["outvec"] : "eigenvectors" + suffix;
@@ -557,6 +579,7 @@ int main(int argc, char *argv[])
       std::string meansdfile = has("outmeansd") ? vm["outmeansd"] : "meansd" + suffix;
       const bool save_meansd = has("outmeansd");
       std::string projfile = has("outproj") ? vm["outproj"] : "projection" + suffix;
+      const std::string uccafile = "ucca" + suffix; // flashpca.cpp:423
 
       int maxiter = 500;
       if (has("maxiter")) {
@@ -627,7 +650,7 @@ int main(int argc, char *argv[])
          return EXIT_FAILURE;
       }
       if (ngpus > 1 && mode != MODE_PCA) {
-         std::cerr << "Error: --gpus applies to PCA only (--check and --project run on one GPU)" << std::endl;
+         std::cerr << "Error: --gpus applies to PCA only (--ucca, --check and --project run on one GPU)" << std::endl;
          return EXIT_FAILURE;
       }
       const int blockvec = has("blockvec") ? (int)to_long(vm, "blockvec") : 0;
@@ -718,6 +741,23 @@ int main(int argc, char *argv[])
       if (bim_error) std::rethrow_exception(bim_error);
       if (N == 0) throw std::runtime_error("no samples found in " + fam_file);
       phase(".fam / .bim");
+      // UCCA: the phenotypes (Data::read_pheno(pheno, 3), data.cpp:408-413), checked against the .fam before any device work.  The
+      // reference takes N from this file's rows and then reads the .bed with that N whatever the .fam says; this build refuses.
+      fpca::TextMatrix pheno;
+      if (mode == MODE_UCCA) {
+         pheno = fpca::read_text(pheno_file, 3);
+         if (pheno.rows != N) {
+            std::cerr << "Error: the phenotype file " << pheno_file << " has " << pheno.rows << " rows, but " << fam_file << " has " << N
+                      << " samples" << std::endl;
+            return EXIT_FAILURE;
+         }
+         if (pheno.cols < 1 || pheno.cols + 2 > N) {
+            std::cerr << "Error: UCCA needs between 1 and N - 2 = " << (N >= 2 ? N - 2 : 0) << " phenotypes, the phenotype file has "
+                      << pheno.cols << std::endl;
+            return EXIT_FAILURE;
+         }
+         phase("phenotypes");
+      }
 
       fpca_ctx *ctx = nullptr;
       uint64_t nsnps = 0; // SNPs in the file (all shards)
@@ -923,7 +963,7 @@ int main(int argc, char *argv[])
       // the reference prints its dense block geometry here (flashpca.cpp:688-690); the whole packed matrix is one resident block
       std::cout << timestamp() << "blocksize: " << nsnps << " (" << (long long)((N + 3) / 4) * (long long)nsnps << " bytes per block)" << std::endl;
 
-      std::vector<double> d, pve, meansd;
+      std::vector<double> d, pve, meansd, ucca_res;
       int k_out = n_dim;
       if (mode == MODE_PCA) {
          std::cout << timestamp() << "PCA begin" << std::endl;
@@ -1016,6 +1056,12 @@ int main(int argc, char *argv[])
          for (int j = 0; j < K; j++)
             verbose && std::cout << timestamp() << "eval(" << (j + 1) << "): " << ev.v[j] << ", sum squared error: " << err[j] << std::endl;
          verbose && std::cout << timestamp() << "Mean squared error: " << mse << ", Root mean squared error: " << rmse << " (n=" << N << ")" << std::endl;
+      } else if (mode == MODE_UCCA) { // flashpca.cpp:729-737 -> RandomPCA::ucca(Data&) (randompca.cpp:567-625)
+         std::cout << timestamp() << "UCCA begin" << std::endl;
+         verbose && std::cout << timestamp() << "UCCA online mode, N=" << N << " p=" << nsnps << std::endl;
+         ucca_res.resize((size_t)nsnps * 3);
+         fpca_ok(fpca_ucca(ctx, pheno.v.data(), (int64_t)N, (int)pheno.cols, stand_method_y, ucca_res.data(), (int64_t)nsnps));
+         std::cout << timestamp() << "UCCA done" << std::endl;
       } else { // MODE_PROJECT: RandomPCA::project (randompca.cpp:745-820)
          fpca::TextMatrix L = fpca::read_text(in_load_file, 3, -1, 1);
          if (L.rows != nsnps) throw std::runtime_error("number of SNPs in the loadings file doesn't match the data");
@@ -1129,6 +1175,9 @@ int main(int argc, char *argv[])
             colnames_pc.assign(k_out + 1, "FID\tIID");
             for (int i = 0; i < k_out; i++) colnames_pc[i + 1] = "PC" + std::to_string(i + 1);
             fpca::save_text(Px.data(), N, k_out, colnames_pc, rownames, projfile, precision);
+         } else if (mode == MODE_UCCA) { // flashpca.cpp:846-852: one row per .bim SNP, named by its id
+            if (snp_ids.size() != nsnps) throw std::runtime_error("the .bim file has a different number of SNPs than the .bed");
+            fpca::save_text(ucca_res.data(), nsnps, 3, {"SNP", "R", "Fstat", "P"}, snp_ids, uccafile, precision);
          }
          if (save_meansd) {
             std::cout << timestamp() << "Writing mean + sd file " << meansdfile << std::endl;

@@ -9,6 +9,7 @@
 //   download.hip        pinned, pipelined result download
 //   hip_backend.hip     BlockBackend over HBM-resident blocks (what solver.cpp drives)
 //   bench_hooks.hip     include/fpca_debug.h: measurement hooks and hardware probes
+//   ucca.hip            fpca_ucca: per-SNP association with k phenotypes through the K2 pass (+ f_tail.hpp, its F tail)
 // MI355X / gfx950 only; there is no CPU fallback anywhere in the library.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -322,6 +322,19 @@ int fpca_pca(fpca_ctx *ctx, const fpca_pca_opts *opts, double *U, double *d, dou
 int fpca_check(fpca_ctx *ctx, const double *evec, int64_t ldu, const double *eval, int k, int divisor,
                double *err, double *mse, double *rmse);
 
+/* ------------------------------------------------------------------------------------------------
+ * Per-SNP association with k phenotypes.  Replaces RandomPCA::ucca(Data&) + wilks (randompca.cpp:103-119, 530-625; flashpca --ucca,
+ * the R function ucca()): a multivariate ANOVA of every SNP of this shard on the phenotypes, in the style of plink.multivariate.
+ * Y is N x k fp64 column-major (leading dimension ldy, NaN = missing), standardised like fpca_create_dense standardises its input
+ * (stand_y: any FPCA_STANDARDISE_*).  With x_j the SNP's standardised column as the PCA path builds it,
+ *   r2_j = || W' x_j ||^2 / || x_j - mean(x_j) 1 ||^2,  W = (Y - 1 mean(Y)') R^-1,  Y = Q R
+ * (exactly the reference's SVD formula), and res (P_g x 3, column-major, leading dimension ldres) receives
+ *   R = sqrt(r2),  Fstat = r2 / (1 - r2) (N - k - 1) / k,  P = upper tail of F(k, N - k - 1) at Fstat.
+ * A SNP without variance gets NaN in all three; r2 >= 1 gives R = 1, Fstat = +inf, P = 0.  The product X_g' W runs through the
+ * context's own arithmetic; a shard's rows are its own SNPs and no collective is issued.  FPCA_EINVAL for k < 1, k > N - 2, a bad
+ * ldy / ldres, an unknown stand_y, a rank-deficient standardised Y, or a context whose mean/sd were preloaded. */
+int fpca_ucca(fpca_ctx *ctx, const double *Y, int64_t ldy, int k, int stand_y, double *res, int64_t ldres);
+
 #ifdef __cplusplus
 }
 #endif

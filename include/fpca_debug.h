@@ -69,6 +69,11 @@ int fpca_debug_k4_fused_bench(fpca_ctx *ctx, int b, int nq, int reps, double *ms
  * reduction) and per block GEMM (Out = Init + sum_q V_q C_q) */
 int fpca_debug_k4_bench(fpca_ctx *ctx, int b, int nq, int reps, double *ms_gram, double *ms_gemm);
 
+/* diagnostic (tests): the F tail of fpca_ucca, from the host build of the same source the finishing kernel runs (no device
+ * involved): F = r2 / (1 - r2) (n - k - 1) / k and P = upper tail of F(k, n - k - 1) at F = I_{1 - r2}((n - k - 1) / 2, k / 2).
+ * FPCA_EINVAL unless k >= 1 and n >= k + 2. */
+int fpca_debug_f_sf(double r2, uint64_t n, int k, double *F, double *P);
+
 #ifdef __cplusplus
 }
 #endif
