@@ -23,6 +23,7 @@ STANDARDISE = {"binom": 2, "binom2": 3}
 STANDARDISE_DENSE = {"none": 0, "sd": 1, "binom": 2, "binom2": 3, "center": 4}
 DIVISOR = {"none": 0, "n1": 1, "p": 2}
 UNIQUE_ID_BYTES = 128
+SCCA_STATUS = {0: "ok", 1: "maxiter reached", 2: "lambda1 too large", 3: "lambda2 too large"}  # FPCA_SCCA_*
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p)
 COLLECTIVE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p)  # all-gather / reduce-scatter
@@ -135,6 +136,9 @@ SIGNATURES = {
     "fpca_pca": (_I, [_P, C.POINTER(PcaOpts), _P, _P, _P, _P, _P, _P, C.POINTER(PcaInfo)]),
     "fpca_check": (_I, [_P, _P, C.c_int64, _P, _I, _I, _P, C.POINTER(_D), C.POINTER(_D)]),
     "fpca_ucca": (_I, [_P, _P, C.c_int64, _I, _I, _P, C.c_int64]),
+    "fpca_scca_prepare": (_I, [_P, _P, C.c_int64, _I, _I, _I]),
+    "fpca_scca_fit": (_I, [_P, _D, _D, _I, _I, _D, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64,
+                           C.POINTER(_I), _P, _P, _P, C.POINTER(_I)]),
     "fpca_bench_apply": (_I, [_P, _I, _I, _I, C.POINTER(BenchResult)]),
     "fpca_profile_begin": (_I, [_P, _I]),
     "fpca_profile_sample_every": (_I, [_P, _I]),

@@ -244,6 +244,46 @@ class Context:
         check(lib().fpca_ucca(self.h, _p(Y), Y.shape[0], Y.shape[1], _lib.STANDARDISE_DENSE[standy], _p(res), self.P))
         return res
 
+    def scca_prepare(self, Y, standy="sd", divisor="n1"):
+        """fpca_scca_prepare: standardise the N x k phenotypes Y (NaN = missing) by `standy`, scale by 1 / sqrt(N - 1) for divisor
+        "n1", and form C = X'Y on the device with one pass over the genotypes; kept until the next scca_prepare or close()."""
+        if standy not in _lib.STANDARDISE_DENSE:
+            raise ValueError("standy must be one of %s" % sorted(_lib.STANDARDISE_DENSE))
+        if divisor not in ("n1", "none"):
+            raise ValueError("divisor must be 'n1' or 'none'")
+        Y = np.asarray(Y, dtype=np.float64)
+        Y = np.asfortranarray(Y.reshape(-1, 1) if Y.ndim == 1 else Y)
+        if Y.ndim != 2 or Y.shape[0] != self.N:
+            raise ValueError("Y must have %d rows (one per sample), it has %d" % (self.N, Y.shape[0]))
+        check(lib().fpca_scca_prepare(self.h, _p(Y), Y.shape[0], Y.shape[1], _lib.STANDARDISE_DENSE[standy], DIVISOR[divisor]))
+        self._scca_k = Y.shape[1]
+
+    def scca_fit(self, lambda1, lambda2, ndim, V0, maxiter=1000, tol=1e-4):
+        """fpca_scca_fit: one sparse CCA model on the prepared phenotypes from the k x ndim starting vectors V0 (RandomPCA::scca,
+        randompca.cpp:387-528).  Returns U (P x ndim), V (k x ndim), d, Px, Py (N x ndim), converged, iters, nzero_x, nzero_y and
+        status ("ok", "maxiter reached", "lambda1 too large", "lambda2 too large")."""
+        k = getattr(self, "_scca_k", None)
+        V0 = np.asarray(V0, dtype=np.float64)
+        V0 = np.asfortranarray(V0.reshape(-1, 1) if V0.ndim == 1 else V0)
+        ndim = int(ndim)
+        if k is not None and ndim >= 1 and V0.shape != (k, ndim):
+            raise ValueError("dimensions of V must be (ncol(Y) x (ndim))")
+        n = max(ndim, 1)
+        U = np.full((self.P, n), np.nan, order="F")
+        V = np.full((max(k or 1, 1), n), np.nan, order="F")
+        d = np.full(n, np.nan)
+        Px = np.full((self.N, n), np.nan, order="F")
+        Py = np.full((self.N, n), np.nan, order="F")
+        conv, status = C.c_int(0), C.c_int(0)
+        iters = np.zeros(n, dtype=np.intc)
+        nzx = np.zeros(n, dtype=np.int64)
+        nzy = np.zeros(n, dtype=np.int64)
+        check(lib().fpca_scca_fit(self.h, float(lambda1), float(lambda2), ndim, int(maxiter), float(tol), _p(V0), V0.shape[0], _p(U), self.P,
+                                  _p(V), V.shape[0], _p(d), _p(Px), self.N, _p(Py), self.N, C.byref(conv), _p(iters), _p(nzx), _p(nzy),
+                                  C.byref(status)))
+        return dict(U=U, V=V, d=d, Px=Px, Py=Py, converged=bool(conv.value), iters=iters, nzero_x=nzx, nzero_y=nzy,
+                    status=_lib.SCCA_STATUS[status.value])
+
     # ---- measurement -----------------------------------------------------------------------------------
     def bench_apply(self, b=32, steps=10, warmup=2):
         r = BenchResult()
@@ -384,6 +424,98 @@ def ucca(X, Y, standx="binom2", standy="binom2", check_geno=True, check_fam=True
     if isinstance(X, str):
         out["snp_ids"] = _read_bim(X)[0]
     return out
+
+
+def scca(X, Y, lambda1=0, lambda2=0, standx="binom2", standy="binom2", ndim=10, divisor="n1", maxiter=1000, tol=1e-4, seed=1,
+         V=None, check_geno=True, check_fam=True, simplify=True, device=0, verbose=False):
+    """Sparse canonical correlation analysis; mirrors scca() of the reference's R package (flashpcaR/R/scca.R:98-316): same
+    arguments and defaults, its stop() checks raised as ValueError with R's wording.
+
+    X: PLINK root name (standx binom or binom2), or a numeric N x P matrix (NaN = missing; any of the five standardisations).
+    Y: N x k phenotypes (NaN = missing, mean-imputed).  lambda1 / lambda2: scalars or vectors of penalties.  V: k x ndim starting
+    vectors; None takes R's warm start -- one fit at lambda1 = lambda2 = 1e-9 from a Gaussian matrix drawn from `seed` (numpy's
+    generator, not the reference's), whose V starts every model.
+    Returns the model (U, V, d, Px, Py, converged, iters, nzero_x, nzero_y, status) when both penalties are scalars and `simplify`,
+    else the nested list res[i][j] of the models at lambda1[i], lambda2[j].  The genotypes are read once, whatever the grid.
+    """
+    import warnings
+
+    standx = _match_arg("standx", standx)
+    standy = _match_arg("standy", standy)
+    if divisor not in ("n1", "none"):
+        raise ValueError("'arg' should be one of \"n1\", \"none\" (divisor)")
+    try:
+        Y = np.asarray(Y, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("Y must be a numeric matrix")
+    if Y.ndim == 1:
+        Y = Y.reshape(-1, 1)  # R: cbind(Y)
+    if Y.ndim != 2:
+        raise ValueError("Y must be a numeric matrix")
+    if np.isnan(Y).any():
+        warnings.warn("Y cantains missing values, will be mean imputed")
+    if isinstance(X, str):
+        if standx not in STANDARDISE:
+            raise ValueError("When using PLINK data, you must use standx='binom' or 'binom2'")
+        n = count_fam_rows(X + ".fam")
+        p = len(_read_bim(X)[0])
+        if check_fam and Y.shape[0] != n:
+            raise ValueError("The number of rows in %s.fam and Y don't match" % X)
+    else:
+        try:
+            X = np.asarray(X, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("X must be a numeric matrix or a string naming a PLINK fileset")
+        if X.ndim != 2:
+            raise ValueError("X must be a numeric matrix or a string naming a PLINK fileset")
+        if np.isnan(X).any():
+            warnings.warn("X cantains missing values, will be mean imputed")
+        if X.shape[1] < 2:
+            raise ValueError("X must have at least two columns")
+        if X.shape[0] < 2:
+            raise ValueError("X must have at least two rows")
+        if Y.shape[0] != X.shape[0]:
+            raise ValueError("The number of rows in X and Y don't match")
+        if standx in STANDARDISE and check_geno and not _is_012(X):
+            raise ValueError("Your data contains values other than {0, 1, 2}, standx='binom'/'binom2' can't be used here")
+        n, p = X.shape
+    l1 = None if lambda1 is None else np.atleast_1d(np.asarray(lambda1, dtype=np.float64))
+    l2 = None if lambda2 is None else np.atleast_1d(np.asarray(lambda2, dtype=np.float64))
+    if l1 is None or np.any(l1 < 0):
+        raise ValueError("lambda1 must be non-negative")
+    if l2 is None or np.any(l2 < 0):
+        raise ValueError("lambda2 must be non-negative")
+    if ndim < 1:
+        raise ValueError("ndim can't be less than 1")
+    max_dim = min(p, n, Y.shape[1], Y.shape[0])
+    if ndim > max_dim:
+        raise ValueError("You asked for %d dimensions, but only %d allowed" % (ndim, max_dim))
+    if V is not None:
+        V = np.asarray(V, dtype=np.float64)
+        if V.ndim == 1:
+            V = V.reshape(-1, 1)  # R: cbind(V)
+        if V.shape != (Y.shape[1], ndim):
+            raise ValueError("dimensions of V must be (ncol(Y) x (ndim))")
+    if isinstance(X, str):
+        ctx = Context.from_bed(X + ".bed", n, stand=standx, device=device, accum="auto")
+    else:
+        ctx = Context.from_dense(X, stand=standx, device=device)
+    with ctx:
+        ctx.scca_prepare(Y, standy=standy, divisor=divisor)
+        if V is None:
+            if verbose:
+                print("initialising V")
+            V0 = np.random.default_rng(seed).standard_normal((Y.shape[1], ndim))
+            V = ctx.scca_fit(1e-9, 1e-9, ndim, V0, maxiter=maxiter, tol=tol)["V"]
+        res = [[ctx.scca_fit(a, b, ndim, V, maxiter=maxiter, tol=tol) for b in l2] for a in l1]
+    if isinstance(X, str):
+        ids = _read_bim(X)[0]
+        for row in res:
+            for m in row:
+                m["snp_ids"] = ids  # R: rownames(s$U) <- bim$V2
+    if simplify and len(l1) == 1 and len(l2) == 1:
+        return res[0][0]
+    return res
 
 
 def _read_bim(prefix):

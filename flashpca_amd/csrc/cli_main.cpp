@@ -4,7 +4,8 @@
 // suffix .txt), same stdout milestones and the same output files/format (eigenvalues / eigenvectors / pcs / pve
 // [/ loadings / meansd], flashpca.cpp:755-878).  Host C++ only: all arithmetic goes through the C ABI of libfpca.so
 // (include/fpca.h); there is no CPU compute path.  Besides PCA, --check and --project, --ucca (per-SNP association with the
-// --pheno phenotypes, RandomPCA::ucca) runs on one GPU; --scca is refused.
+// --pheno phenotypes, RandomPCA::ucca) runs on one GPU; --scca is refused (the library has sparse CCA, fpca_scca_prepare /
+// fpca_scca_fit; the flag and its output files are not wired to it).
 // New, MI355X-specific flags: --device, --blockvec, --maxblocks, --accum.  --memory/--blocksize/--batch/--numthreads are
 // accepted for compatibility; the packed matrix is always fully resident in HBM so they have no effect.
 #include <cerrno>

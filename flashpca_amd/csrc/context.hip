@@ -126,6 +126,7 @@ void ctx_free(fpca_ctx *c)
 {
    if (!c) return;
    (void)hipSetDevice(c->device);
+   scca_free(c);
    if (c->comm) {
       try {
          rccl().CommDestroy(c->comm);

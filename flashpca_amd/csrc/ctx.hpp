@@ -10,6 +10,7 @@
 //   hip_backend.hip     BlockBackend over HBM-resident blocks (what solver.cpp drives)
 //   bench_hooks.hip     include/fpca_debug.h: measurement hooks and hardware probes
 //   ucca.hip            fpca_ucca: per-SNP association with k phenotypes through the K2 pass (+ f_tail.hpp, its F tail)
+//   scca.hip            fpca_scca_prepare / fpca_scca_fit: sparse CCA iterated on the resident P x k matrix C = X'Y
 // MI355X / gfx950 only; there is no CPU fallback anywhere in the library.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -78,6 +79,7 @@ RcclApi &rccl();
 } // namespace fpca
 
 using fpca::RowShard;
+struct fpca_scca_state; // scca.hip: C = X'Y and the phenotypes of the last fpca_scca_prepare
 
 // ---- the context ---------------------------------------------------------------------------------------
 struct fpca_ctx {
@@ -199,6 +201,7 @@ struct fpca_ctx {
    std::vector<hipEvent_t> prof_ev;
    int prof_used = 0, prof_calls = 0, prof_stride = 1; // every prof_stride-th apply carries the events
    bool prof_on = false;
+   fpca_scca_state *scca = nullptr; // released by the next fpca_scca_prepare or by fpca_destroy (scca_free)
 
    void ensure(double *&p, size_t &cap, size_t need); // grow a device workspace of doubles (context.hip)
    bool multi() const { return comm != nullptr || ar_fn != nullptr || comm_dead; }
@@ -266,6 +269,9 @@ void apply_xxt_dev(fpca_ctx *c, const double *dB, int b, double *dY, hipStream_t
 void apply_sharded(fpca_ctx *c, const RowShard &sh, const double *in_slice, int b, double *out_slice, hipStream_t s);
 void xt_dev(fpca_ctx *c, const double *dB, int b, hipStream_t s); // T (in the context) = X_g' dB
 void x_dev(fpca_ctx *c, int b, double *dY, hipStream_t s);        // dY = X_g T
+
+// ---- scca.hip ---------------------------------------------------------------------------------------------
+void scca_free(fpca_ctx *c);
 
 // ---- download.hip -----------------------------------------------------------------------------------------
 // d_img: device, column-major N x ncols with leading dimension N -> host (ld) and, scaled per column, host2 (ld2); synchronises

@@ -335,6 +335,41 @@ int fpca_check(fpca_ctx *ctx, const double *evec, int64_t ldu, const double *eva
  * ldy / ldres, an unknown stand_y, a rank-deficient standardised Y, or a context whose mean/sd were preloaded. */
 int fpca_ucca(fpca_ctx *ctx, const double *Y, int64_t ldy, int k, int stand_y, double *res, int64_t ldres);
 
+/* ------------------------------------------------------------------------------------------------
+ * Sparse canonical correlation analysis of the genotypes with k phenotypes.  Replaces RandomPCA::scca(Data&, ...)
+ * (randompca.cpp:387-528, norm_thresh :225-245; the R function scca()).  The reference makes two passes over the genotypes per
+ * iteration; here fpca_scca_prepare forms C = invdiv X' Yh (P_g x k, fp64) with ONE pass and keeps it on the device, and every
+ * fpca_scca_fit -- one per penalty pair of a grid -- iterates on C alone and ends with one pass for Px.
+ *
+ * fpca_scca_prepare (randompca.cpp:402-415): Y is N x k fp64 column-major (leading dimension ldy, NaN = missing), standardised
+ * like fpca_create_dense standardises its input (stand_y: any FPCA_STANDARDISE_*); Yh = that * invdiv, invdiv = 1 / sqrt(N - 1)
+ * for divisor FPCA_DIVISOR_N1 and 1 for every other value.  C and Yh stay with the context until the next fpca_scca_prepare or
+ * fpca_destroy.  FPCA_ENOMEM (with the size in the message) when C does not fit; FPCA_EINVAL for k < 1, k > 3840, a bad ldy, an
+ * unknown stand_y, or a context that is one shard of several (a communicator, an all-reduce hook, fpca_set_rank with nranks > 1:
+ * the normalisation of u spans all SNPs). */
+int fpca_scca_prepare(fpca_ctx *ctx, const double *Y, int64_t ldy, int k, int stand_y, int divisor);
+/* fpca_scca_fit (randompca.cpp:417-528): from V0 (k x ndim, leading dimension ldv0, required), for each dimension j
+ *     u <- C v_j, sequential Gram-Schmidt against U[:, <j], norm_thresh(u, lambda1)
+ *     v <- C'u,   sequential Gram-Schmidt against V[:, <j], norm_thresh(v, lambda2)
+ * until iter > 0 and max |u - u_old| < tol and max |v - v_old| < tol, at most maxiter iterations; d_j = u'C v.
+ * Outputs (host, column-major, caller-allocated; any may be NULL): U P_g x ndim, V k x ndim, d ndim, Px = invdiv X U and
+ * Py = Yh V (N x ndim each), *converged, iters[ndim] (the reference's "dim j finished in ... iterations"), nzero_x / nzero_y[ndim]
+ * (non-zeros of every column of U / V, randompca.cpp:509-510), *status = FPCA_SCCA_*.
+ * The call SUCCEEDS with *converged = 0 when
+ *   - maxiter is reached in dimension j (FPCA_SCCA_MAXITER): its current u, v stay in U, V, d_j = 0, no later dimension is
+ *     attempted (U zero, V as in V0, d zero there, iters zero); Px and Py are computed from what is there;
+ *   - all of u (or v) is below tol in absolute value after norm_thresh (FPCA_SCCA_LAMBDA1_TOO_LARGE / _LAMBDA2_): the finished
+ *     dimensions are kept, column j and the later ones are U zero, V as in V0, d zero.
+ * FPCA_EINVAL: no fpca_scca_prepare before, ndim outside 1 .. min(N, P_g, k), lambda1 / lambda2 < 0, tol <= 0, maxiter < 1, V0
+ * NULL or not finite, a leading dimension too small, a context that is one shard of several. */
+#define FPCA_SCCA_OK 0
+#define FPCA_SCCA_MAXITER 1
+#define FPCA_SCCA_LAMBDA1_TOO_LARGE 2
+#define FPCA_SCCA_LAMBDA2_TOO_LARGE 3
+int fpca_scca_fit(fpca_ctx *ctx, double lambda1, double lambda2, int ndim, int maxiter, double tol, const double *V0, int64_t ldv0,
+                  double *U, int64_t ldu, double *V, int64_t ldv, double *d, double *Px, int64_t ldpx, double *Py, int64_t ldpy,
+                  int *converged, int *iters, int64_t *nzero_x, int64_t *nzero_y, int *status);
+
 #ifdef __cplusplus
 }
 #endif
