@@ -139,6 +139,8 @@ SIGNATURES = {
     "fpca_scca_prepare": (_I, [_P, _P, C.c_int64, _I, _I, _I]),
     "fpca_scca_fit": (_I, [_P, _D, _D, _I, _I, _D, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64,
                            C.POINTER(_I), _P, _P, _P, C.POINTER(_I)]),
+    "fpca_scca_cv": (_I, [_P, _P, C.c_int64, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _D, _P, C.c_int64, C.c_int64, _D, _I, _P, _P, _P, _P, _P, _P,
+                          C.POINTER(_D), C.POINTER(_D), C.POINTER(_D), _P, _P]),
     "fpca_bench_apply": (_I, [_P, _I, _I, _I, C.POINTER(BenchResult)]),
     "fpca_profile_begin": (_I, [_P, _I]),
     "fpca_profile_sample_every": (_I, [_P, _I]),
@@ -152,6 +154,7 @@ SIGNATURES = {
     "fpca_debug_k4_fused": (_I, [_P, _I, _I, _P, _P, _P, _P, _P]),
     "fpca_debug_k4_fused_bench": (_I, [_P, _I, _I, _I, C.POINTER(_D)]),
     "fpca_debug_f_sf": (_I, [_D, _U64, _I, C.POINTER(_D), C.POINTER(_D)]),
+    "fpca_debug_fold_stats": (_I, [_P, _P, _I, _P, _I, _P]),
 }
 
 ABI_VERSION = 4  # FPCA_ABI_VERSION of the include/fpca.h the structures above mirror

@@ -284,6 +284,67 @@ class Context:
         return dict(U=U, V=V, d=d, Px=Px, Py=Py, converged=bool(conv.value), iters=iters, nzero_x=nzx, nzero_y=nzy,
                     status=_lib.SCCA_STATUS[status.value])
 
+    def scca_cv(self, Y, folds, lambda1, lambda2, ndim, V0, standy="sd", divisor="n1", maxiter=1000, tol=1e-4, warm_lambda=1e-12, opt_dim=1,
+                return_pred=False):
+        """fpca_scca_cv: K-fold cross-validation of the SCCA penalties (the R function cv.scca(), flashpcaR/R/scca.R:410-557) on this
+        context's packed genotypes.  folds: one id in 0 .. nfolds - 1 per sample; V0: (nfolds, k, ndim), or (k, ndim) for every fold;
+        warm_lambda < 0 (or None): no warm start.  Returns corr, nzero_x, nzero_y (ndim, n1, n2), converged (nfolds, n1, n2), iters
+        (nfolds, n1, n2, ndim), warm_iters (nfolds, ndim), best_lambda1, best_lambda2, best_corr and, with return_pred, xpred / ypred
+        (N, ndim, n1, n2)."""
+        if standy not in _lib.STANDARDISE_DENSE:
+            raise ValueError("standy must be one of %s" % sorted(_lib.STANDARDISE_DENSE))
+        if divisor not in ("n1", "none"):
+            raise ValueError("divisor must be 'n1' or 'none'")
+        Y = np.asarray(Y, dtype=np.float64)
+        Y = np.asfortranarray(Y.reshape(-1, 1) if Y.ndim == 1 else Y)
+        if Y.ndim != 2 or Y.shape[0] != self.N:
+            raise ValueError("Y must have %d rows (one per sample), it has %d" % (self.N, Y.shape[0]))
+        k, ndim = Y.shape[1], int(ndim)
+        folds = np.asarray(folds)
+        if folds.shape != (self.N,):
+            raise ValueError("'folds' must be of same number of rows as X and Y")
+        if folds.min() < 0 or folds.max() > 255:
+            raise ValueError("fold ids must be in 0 .. 63")
+        nfolds = int(folds.max()) + 1
+        folds8 = np.ascontiguousarray(folds, dtype=np.uint8)
+        l1 = np.ascontiguousarray(np.atleast_1d(lambda1), dtype=np.float64)
+        l2 = np.ascontiguousarray(np.atleast_1d(lambda2), dtype=np.float64)
+        n1, n2, nd = l1.size, l2.size, max(ndim, 1)
+        V0 = np.asarray(V0, dtype=np.float64)
+        if V0.ndim == 2:
+            V0 = V0[None]
+        if V0.ndim != 3 or V0.shape[1:] != (k, nd) or V0.shape[0] not in (1, nfolds):
+            raise ValueError("dimensions of V must be (ncol(Y) x (ndim)), one matrix per fold")
+        V0 = np.ascontiguousarray(V0.transpose(0, 2, 1))  # [fold][dimension][phenotype]: column-major k x ndim matrices
+        corr = np.full((nd, n1, n2), np.nan)
+        nzx = np.full((nd, n1, n2), np.nan)
+        nzy = np.full((nd, n1, n2), np.nan)
+        conv = np.zeros((nfolds, n1, n2), dtype=np.intc)
+        iters = np.zeros((nfolds, n1, n2, nd), dtype=np.intc)
+        witers = np.zeros((nfolds, nd), dtype=np.intc)
+        b1, b2, bc = C.c_double(np.nan), C.c_double(np.nan), C.c_double(np.nan)
+        xp = np.empty((n1, n2, nd, self.N)) if return_pred else None
+        yp = np.empty((n1, n2, nd, self.N)) if return_pred else None
+        check(lib().fpca_scca_cv(self.h, _p(Y), Y.shape[0], k, _p(folds8), nfolds, _p(l1), n1, _p(l2), n2, ndim, _lib.STANDARDISE_DENSE[standy],
+                                 DIVISOR[divisor], int(maxiter), float(tol), _p(V0), k, k * nd if V0.shape[0] > 1 else 0,
+                                 -1.0 if warm_lambda is None else float(warm_lambda), int(opt_dim), _p(corr), _p(nzx), _p(nzy), _p(conv), _p(iters),
+                                 _p(witers), C.byref(b1), C.byref(b2), C.byref(bc), _p(xp), _p(yp)))
+        out = dict(corr=corr, nzero_x=nzx, nzero_y=nzy, converged=conv.astype(bool), iters=iters, warm_iters=witers, best_lambda1=b1.value,
+                   best_lambda2=b2.value, best_corr=bc.value)
+        if return_pred:
+            out["xpred"], out["ypred"] = xp.transpose(3, 2, 0, 1), yp.transpose(3, 2, 0, 1)
+        return out
+
+    def fold_stats(self, folds, nfolds, which_fold=None):
+        """fpca_debug_fold_stats: counts (nfolds, P, 3) of the samples of every fold with dosage 0 / 1 / 2 and, for which_fold, the
+        (P, 2) mean / sd over the samples outside it as scca_cv installs them."""
+        folds8 = np.ascontiguousarray(folds, dtype=np.uint8)
+        assert folds8.shape == (self.N,)
+        counts = np.zeros((nfolds, self.P, 3), dtype=np.uint32)
+        ms = np.empty((self.P, 2), order="F") if which_fold is not None else None
+        check(lib().fpca_debug_fold_stats(self.h, _p(folds8), int(nfolds), _p(counts), -1 if which_fold is None else int(which_fold), _p(ms)))
+        return counts, ms
+
     # ---- measurement -----------------------------------------------------------------------------------
     def bench_apply(self, b=32, steps=10, warmup=2):
         r = BenchResult()
@@ -516,6 +577,125 @@ def scca(X, Y, lambda1=0, lambda2=0, standx="binom2", standy="binom2", ndim=10, 
     if simplify and len(l1) == 1 and len(l2) == 1:
         return res[0][0]
     return res
+
+
+def pack_dosages(X):
+    """A numeric N x P matrix of {0, 1, 2, NaN} -> PLINK's packed records (P x ceil(N / 4) bytes; codes 3, 2, 0 and 1 = missing)."""
+    X = np.asarray(X, dtype=np.float64)
+    n, p = X.shape
+    codes = np.ones(((n + 3) // 4 * 4, p), dtype=np.uint8)  # missing
+    codes[:n][X == 0] = 3
+    codes[:n][X == 1] = 2
+    codes[:n][X == 2] = 0
+    codes[n:] = 0  # PLINK writes the pad bits as 0
+    c = codes.T
+    return np.ascontiguousarray(c[:, 0::4] | (c[:, 1::4] << 2) | (c[:, 2::4] << 4) | (c[:, 3::4] << 6))
+
+
+def cv_scca(X, Y, lambda1=np.linspace(1e-6, 1e-3, 5), lambda2=np.linspace(1e-6, 1e-3, 5), ndim=3, nfolds=10, folds=None, opt_dim=1, init=True,
+            standx="binom2", standy="binom2", divisor="n1", maxiter=1000, tol=1e-4, seed=1, device=0, verbose=False, return_pred=False):
+    """Cross-validation of the SCCA penalties; mirrors cv.scca() of the reference's R package (flashpcaR/R/scca.R:410-557): same
+    arguments and defaults, its stop() checks (and those of scca() that apply) raised as ValueError with R's wording before any
+    device work.
+
+    X: PLINK root name, or a numeric N x P matrix of {0, 1, 2, NaN}, which is packed on the host; standx binom or binom2 -- every fold
+    standardises the genotypes on its training samples, which needs genotype input (R supports numeric matrices only and standardises
+    the held-out rows with everything).  folds: ids 1 .. nfolds as in R (overrides nfolds); None draws them from `seed`, and each
+    fold's starting matrix from the same generator.  init: R's warm start at 1e-12; False starts from scca()'s own at 1e-9.
+    Returns R's fields (ndim, lambda1, lambda2, opt_dim, best_lambda1, best_lambda2, best_corr, corr, nzero_x, nzero_y, nfolds,
+    converged) plus iters, warm_iters, folds and, with return_pred, xpred / ypred (N, ndim, n1, n2)."""
+    import warnings
+
+    standx = _match_arg("standx", standx)
+    standy = _match_arg("standy", standy)
+    if divisor not in ("n1", "none"):
+        raise ValueError("'arg' should be one of \"n1\", \"none\" (divisor)")
+    try:
+        Y = np.asarray(Y, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("Y must be a numeric matrix")
+    if Y.ndim == 1:
+        Y = Y.reshape(-1, 1)  # R: cbind(Y)
+    if Y.ndim != 2:
+        raise ValueError("Y must be a numeric matrix")
+    n = Y.shape[0]
+    if nfolds > n:
+        raise ValueError("nfolds is too large for the number of samples")
+    if opt_dim <= 0 or opt_dim > ndim:
+        raise ValueError("opt.dim must be between 1 and ndim")
+    if not isinstance(init, (bool, np.bool_)):
+        raise ValueError("init muct be TRUE or FALSE")
+    if folds is not None:
+        try:
+            folds = np.asarray(folds).astype(np.int64).ravel()
+        except (TypeError, ValueError):
+            raise ValueError("'folds' must be a set of contiguous integers from 1 to nfolds")
+        if folds.size != n:
+            raise ValueError("'folds' must be of same number of rows as X and Y")
+        if np.any(np.diff(np.sort(folds)) > 1) or folds.min() < 1:
+            raise ValueError("'folds' must be a set of contiguous integers from 1 to nfolds")
+        warnings.warn("'folds' will override 'nfolds' parameter")
+        nfolds = int(folds.max())
+    if np.isnan(Y).any():
+        warnings.warn("Y cantains missing values, will be mean imputed")
+    if standx not in STANDARDISE:
+        raise ValueError("Cross-validation re-standardises the genotypes on every fold's training samples and needs genotype input: "
+                         "standx must be 'binom' or 'binom2'")
+    if isinstance(X, str):
+        nx = count_fam_rows(X + ".fam")
+        p = len(_read_bim(X)[0])
+        if Y.shape[0] != nx:
+            raise ValueError("The number of rows in %s.fam and Y don't match" % X)
+    else:
+        try:
+            X = np.asarray(X, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("X must be a numeric matrix or a string naming a PLINK fileset")
+        if X.ndim != 2:
+            raise ValueError("X must be a numeric matrix or a string naming a PLINK fileset")
+        if X.shape[1] < 2:
+            raise ValueError("X must have at least two columns")
+        if X.shape[0] < 2:
+            raise ValueError("X must have at least two rows")
+        if Y.shape[0] != X.shape[0]:
+            raise ValueError("The number of rows in X and Y don't match")
+        if not _is_012(X):
+            raise ValueError("Your data contains values other than {0, 1, 2}; cross-validation re-standardises the genotypes on every "
+                             "fold's training samples and needs genotype input")
+        if np.isnan(X).any():
+            warnings.warn("X cantains missing values, will be mean imputed")
+        p = X.shape[1]
+    if standy in STANDARDISE and not _is_012(Y):
+        raise ValueError("Your data contains values other than {0, 1, 2}, standy='binom'/'binom2' can't be used here")
+    l1 = None if lambda1 is None else np.atleast_1d(np.asarray(lambda1, dtype=np.float64))
+    l2 = None if lambda2 is None else np.atleast_1d(np.asarray(lambda2, dtype=np.float64))
+    if l1 is None or l1.size == 0 or not np.all(l1 >= 0):
+        raise ValueError("lambda1 must be non-negative")
+    if l2 is None or l2.size == 0 or not np.all(l2 >= 0):
+        raise ValueError("lambda2 must be non-negative")
+    if ndim < 1:
+        raise ValueError("ndim can't be less than 1")
+    rng = np.random.default_rng(seed)
+    if folds is None:
+        folds = rng.integers(1, nfolds + 1, n)
+    if nfolds < 2 or nfolds > 64:
+        raise ValueError("between 2 and 64 folds are supported, not %d" % nfolds)
+    min_train = n - int(np.bincount(folds, minlength=nfolds + 1).max())
+    max_dim = min(p, min_train, Y.shape[1])
+    if ndim > max_dim:
+        raise ValueError("You asked for %d dimensions, but only %d allowed" % (ndim, max_dim))
+    V0 = rng.standard_normal((nfolds, Y.shape[1], ndim))  # scca.R:478: a fresh Gaussian matrix per fold
+    if isinstance(X, str):
+        ctx = Context.from_bed(X + ".bed", n, stand=standx, device=device, accum="auto")
+    else:
+        ctx = Context.from_packed(pack_dosages(X), n, p, stand=standx, device=device, accum="auto")
+    with ctx:
+        if verbose:
+            print("cv.scca: N=%d p=%d, %d folds, %d x %d penalties" % (ctx.N, ctx.P, nfolds, l1.size, l2.size))
+        r = ctx.scca_cv(Y, folds - 1, l1, l2, ndim, V0, standy=standy, divisor=divisor, maxiter=maxiter, tol=tol,
+                        warm_lambda=1e-12 if init else 1e-9, opt_dim=opt_dim, return_pred=return_pred)
+    r.update(ndim=ndim, lambda1=l1, lambda2=l2, opt_dim=opt_dim, nfolds=nfolds, folds=folds)
+    return r
 
 
 def _read_bim(prefix):

@@ -10,7 +10,8 @@
 //   hip_backend.hip     BlockBackend over HBM-resident blocks (what solver.cpp drives)
 //   bench_hooks.hip     include/fpca_debug.h: measurement hooks and hardware probes
 //   ucca.hip            fpca_ucca: per-SNP association with k phenotypes through the K2 pass (+ f_tail.hpp, its F tail)
-//   scca.hip            fpca_scca_prepare / fpca_scca_fit: sparse CCA iterated on the resident P x k matrix C = X'Y
+//   scca.hip            fpca_scca_prepare / fpca_scca_fit: sparse CCA iterated on the resident P x k matrix C = X'Y (+ scca.hpp)
+//   scca_cv.hip         fpca_scca_cv: K-fold cross-validation of the SCCA penalties, per-fold statistics from one pass over the packed stream
 // MI355X / gfx950 only; there is no CPU fallback anywhere in the library.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -27,32 +27,14 @@
 #include <memory>
 
 #include "ctx.hpp"
+#include "scca.hpp"
 
 using namespace fpca;
-
-// what a context keeps between fpca_scca_prepare and fpca_scca_fit
-struct fpca_scca_state {
-   int k = 0, kp = 0;
-   double invdiv = 1;
-   double *d_C = nullptr;       // [P_g][kp]
-   std::vector<double> Yh;      // N x k column-major: the standardised phenotypes * invdiv (Py = Yh V is a host product)
-   // workspaces of the fits, grown on demand
-   double *d_ws = nullptr;
-   size_t ws_cap = 0;
-   int *d_flags = nullptr; // [0] done (0 running, 1 converged, 2 u vanished, 3 v vanished), [1] iterations completed
-   ~fpca_scca_state()
-   {
-      if (d_C) (void)hipFree(d_C);
-      if (d_ws) (void)hipFree(d_ws);
-      if (d_flags) (void)hipFree(d_flags);
-   }
-};
 
 namespace {
 
 constexpr int RB = 256;    // rows of C per workgroup (16 passes of 16 rows, 16 lanes per row)
 constexpr int BATCH = 16;  // iterations enqueued between two looks at the flags
-constexpr int MAX_K = 3840; // k_scca_v keeps w and v (2 * k_pad doubles) in LDS
 constexpr int DONE_CONVERGED = 1, DONE_U_ZERO = 2, DONE_V_ZERO = 3;
 
 // sums / maxima over the NW waves of a workgroup in a fixed order, the result in every thread (red: NW doubles of LDS)
@@ -88,7 +70,7 @@ template <int NW> __device__ __forceinline__ double sum_partials(const double *p
    return block_sum<NW>(s, red);
 }
 
-// T (where K2 left a chunk, [P_pad][b] row-major) -> columns [c0, c0 + bw) of C, scaled; columns >= nc of the chunk are C's zero pad
+// T (where K2 left a chunk, [P_pad][b] row-major) -> columns [c0, min(c0 + b, kp)) of C, scaled; columns >= nc of the chunk are C's zero pad
 __global__ __launch_bounds__(256) void k_scca_store_c(const double *__restrict__ T, uint64_t P_g, int b, int nc, double scale,
                                                       double *__restrict__ Cm, int kp, int c0)
 {
@@ -96,6 +78,7 @@ __global__ __launch_bounds__(256) void k_scca_store_c(const double *__restrict__
    if (i >= P_g * (uint64_t)b) return;
    const uint64_t j = i / b;
    const int c = (int)(i % b);
+   if (c0 + c >= kp) return; // (a chunk wider than C's own pad: fpca_scca_cv never passes 48 columns to K2)
    Cm[j * kp + c0 + c] = c < nc ? scale * T[i] : 0.0;
 }
 
@@ -354,16 +337,24 @@ __global__ __launch_bounds__(256) void k_scca_gram_sum(const double *partG, int 
    }
 }
 
-void check_single(const fpca_ctx *c, const char *fn)
+} // namespace
+
+namespace fpca {
+
+void scca_check_single(const fpca_ctx *c, const char *fn)
 {
    if (c->multi() || (c->rank_known && c->nranks > 1))
       throw Error(FPCA_EINVAL, std::string(fn) + ": the context is one shard of several (a communicator, an all-reduce hook or fpca_set_rank with " +
                                    "more than one rank); SCCA normalises u over all SNPs and runs on a single context only");
 }
 
-} // namespace
-
-namespace fpca {
+void scca_store_c(const double *T, uint64_t P_g, int b, int nc, double scale, double *Cm, int kp, int c0, hipStream_t s)
+{
+   const uint64_t tot = P_g * (uint64_t)b;
+   if (!tot) return;
+   hipLaunchKernelGGL(k_scca_store_c, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, T, P_g, b, nc, scale, Cm, kp, c0);
+   HIP_CHECK(hipGetLastError());
+}
 
 void scca_free(fpca_ctx *c)
 {
@@ -421,9 +412,7 @@ static void scca_prepare(fpca_ctx *c, const double *Y, int64_t ldy, int k, int s
       HIP_CHECK(hipMemcpyAsync(c->d_stage, st->Yh.data() + (size_t)c0 * N, (size_t)N * nc * sizeof(double), hipMemcpyHostToDevice, s));
       kern::colmajor_to_block(c->d_stage, N, N, c->N_pad, bw, nc, c->d_io_a, s);
       xt_dev(c, c->d_io_a, bw, s);
-      const uint64_t tot = P * (uint64_t)bw;
-      hipLaunchKernelGGL(k_scca_store_c, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, c->d_T, P, bw, nc, st->invdiv, st->d_C, kp, c0);
-      HIP_CHECK(hipGetLastError());
+      scca_store_c(c->d_T, P, bw, nc, st->invdiv, st->d_C, kp, c0, s);
    }
    HIP_CHECK(hipStreamSynchronize(s));
    c->scca = st.release();
@@ -443,10 +432,10 @@ struct SccaOut {
    int *status;
 };
 
-static void scca_fit(fpca_ctx *c, double lambda1, double lambda2, int ndim, int maxiter, double tol, const double *V0, int64_t ldv0, const SccaOut &o)
+void scca_fit_dev(fpca_ctx *c, fpca_scca_state *st, double lambda1, double lambda2, int ndim, int maxiter, double tol, const double *V0, int64_t ldv0,
+                  SccaDevFit &fit)
 {
-   fpca_scca_state *st = c->scca;
-   const uint64_t N = c->N, P = c->P_g;
+   const uint64_t P = c->P_g;
    const int k = st->k, kp = st->kp;
    HIP_CHECK(hipSetDevice(c->device));
    hipStream_t s = c->stream;
@@ -518,6 +507,26 @@ static void scca_fit(fpca_ctx *c, double lambda1, double lambda2, int ndim, int 
    if (jstop < ndim) // V of the columns never finished: as given
       HIP_CHECK(hipMemcpy2DAsync(dV + (size_t)jstop * kp, (size_t)kp * sizeof(double), V0 + (size_t)jstop * ldv0, (size_t)ldv0 * sizeof(double),
                                  (size_t)k * sizeof(double), ndim - jstop, hipMemcpyHostToDevice, s));
+   fit.dU = dU;
+   fit.dV = dV;
+   fit.d.swap(d);
+   fit.iters.swap(iters);
+   fit.converged = converged;
+   fit.status = status;
+}
+
+static void scca_fit(fpca_ctx *c, double lambda1, double lambda2, int ndim, int maxiter, double tol, const double *V0, int64_t ldv0, const SccaOut &o)
+{
+   fpca_scca_state *st = c->scca;
+   const uint64_t N = c->N, P = c->P_g;
+   const int k = st->k, kp = st->kp;
+   hipStream_t s = c->stream;
+   SccaDevFit fit;
+   scca_fit_dev(c, st, lambda1, lambda2, ndim, maxiter, tol, V0, ldv0, fit);
+   const double *dU = fit.dU, *dV = fit.dV;
+   const std::vector<double> &d = fit.d;
+   const std::vector<int> &iters = fit.iters;
+   const int converged = fit.converged, status = fit.status;
 
    // results.  U and V always come to the host: the non-zero counts and Py are host work
    std::vector<double> hV((size_t)k * ndim), hU_own;
@@ -585,10 +594,10 @@ extern "C" int fpca_scca_prepare(fpca_ctx *ctx, const double *Y, int64_t ldy, in
 {
    return guarded([&] {
       if (!ctx || !Y) throw Error(FPCA_EINVAL, "bad argument to fpca_scca_prepare (NULL pointer)");
-      check_single(ctx, "fpca_scca_prepare");
+      scca_check_single(ctx, "fpca_scca_prepare");
       if (k < 1) throw Error(FPCA_EINVAL, "fpca_scca_prepare needs at least one phenotype (k >= 1)");
-      if (k > MAX_K)
-         throw Error(FPCA_EINVAL, "fpca_scca_prepare: " + std::to_string(k) + " phenotypes; at most " + std::to_string(MAX_K) +
+      if (k > SCCA_MAX_K)
+         throw Error(FPCA_EINVAL, "fpca_scca_prepare: " + std::to_string(k) + " phenotypes; at most " + std::to_string(SCCA_MAX_K) +
                                       " are supported (the k-sized step keeps two vectors of that length in the 64 KB of one workgroup's LDS)");
       if (ldy < (int64_t)ctx->N) throw Error(FPCA_EINVAL, "fpca_scca_prepare: ldy is smaller than the number of samples");
       if (stand_y < FPCA_STANDARDISE_NONE || stand_y > FPCA_STANDARDISE_CENTER)
@@ -604,7 +613,7 @@ extern "C" int fpca_scca_fit(fpca_ctx *ctx, double lambda1, double lambda2, int 
 {
    return guarded([&] {
       if (!ctx) throw Error(FPCA_EINVAL, "bad argument to fpca_scca_fit (NULL context)");
-      check_single(ctx, "fpca_scca_fit");
+      scca_check_single(ctx, "fpca_scca_fit");
       if (!ctx->scca) throw Error(FPCA_EINVAL, "fpca_scca_fit: no phenotypes prepared (call fpca_scca_prepare on this context first)");
       const int k = ctx->scca->k;
       const uint64_t maxdim = std::min<uint64_t>(std::min<uint64_t>(ctx->N, ctx->P_g), (uint64_t)k);

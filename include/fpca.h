@@ -370,6 +370,39 @@ int fpca_scca_fit(fpca_ctx *ctx, double lambda1, double lambda2, int ndim, int m
                   double *U, int64_t ldu, double *V, int64_t ldv, double *d, double *Px, int64_t ldpx, double *Py, int64_t ldpy,
                   int *converged, int *iters, int64_t *nzero_x, int64_t *nzero_y, int *status);
 
+/* ------------------------------------------------------------------------------------------------
+ * K-fold cross-validation of the SCCA penalties on the packed genotypes.  Replaces the R function cv.scca() (flashpcaR/R/scca.R:410-557),
+ * which accepts numeric matrices only; here the packed matrix is the supported input and is never copied: ONE pass counts the
+ * genotypes of every fold, and per fold f (T_f = the samples outside it, H_f = those in it)
+ *   - the per-SNP mean / sd over T_f (the rule of the PCA path, exact integer sums) standardise ALL N rows, the held-out rows
+ *     included, as a projection standardises new samples; Y is standardised on T_f by stand_y the same way (NaN imputed as there);
+ *   - C_f = invdiv_f^2 X[T_f]' Y[T_f] from one K2 pass, invdiv_f = 1 / sqrt(|T_f| - 1) for FPCA_DIVISOR_N1, else 1;
+ *   - if warm_lambda >= 0 the fit at (warm_lambda, warm_lambda) from V0_f gives the V every grid fit of the fold starts from,
+ *     converged or not (scca.R:474-481: 1e-12); warm_lambda < 0: they start from V0_f;
+ *   - the n1 x n2 fits of fpca_scca_fit, edge rules unchanged;
+ *   - xpred[H_f] = X[H_f] U and ypred[H_f] = Y[H_f] V (scca.R:504-505; no invdiv), NaN where the model did not converge.
+ * corr is the Pearson correlation of xpred and ypred over all N samples pooled (scca.R:525-536; NaN when a row is NaN or a variance
+ * is zero), nzero_x / nzero_y the mean over the folds of the non-zero counts of U / V (scca.R:516-523).  best_corr is the largest finite
+ * corr of dimension opt_dim (1-based), best_lambda1 / best_lambda2 its penalties, ties in which()'s order: lambda1's index fastest,
+ * first hit (scca.R:538-547); all three NaN when no cell is finite -- the call still succeeds.
+ * Inputs: Y N x k column-major (ldy); fold[N] in 0 .. nfolds - 1, 2 <= nfolds <= 64 (a fold without samples trains on everything and
+ * predicts nothing, as R's loop does); lambda1[n1], lambda2[n2]; V0: one k x ndim matrix per fold, matrix f at V0 + f * v0_stride,
+ * leading dimension ldv0 (v0_stride 0: one matrix for every fold).
+ * Outputs (host, caller-allocated, any may be NULL), C index order, i over lambda1, j over lambda2, q over dimensions:
+ *   corr, nzero_x, nzero_y [ndim][n1][n2] ....... (q * n1 + i) * n2 + j
+ *   converged [nfolds][n1][n2], iters [nfolds][n1][n2][ndim], warm_iters [nfolds][ndim] (zero without a warm start)
+ *   xpred, ypred: N x (n1 n2 ndim) column-major, leading dimension N, column (i * n2 + j) * ndim + q -- downloaded only if asked for.
+ * The context's mean / sd / table are swapped per fold and restored on every way out, errors included (also a standardisation
+ * preloaded with fpca_set_meansd); the state of an earlier fpca_scca_prepare is RELEASED: fpca_scca_fit needs a new prepare afterwards.
+ * FPCA_EINVAL: what fpca_scca_prepare / fpca_scca_fit refuse; a dense context (fpca_create_dense keeps only its standardised matrix);
+ * nfolds outside 2 .. 64; a fold id >= nfolds; a training set of fewer than 2 samples; ndim outside 1 .. min(smallest |T_f|, P_g, k);
+ * opt_dim outside 1 .. ndim; a negative or non-finite penalty.  FPCA_ENOMEM (with the size in the message) when C, xpred / ypred or a
+ * workspace does not fit. */
+int fpca_scca_cv(fpca_ctx *ctx, const double *Y, int64_t ldy, int k, const uint8_t *fold, int nfolds, const double *lambda1, int n1,
+                 const double *lambda2, int n2, int ndim, int stand_y, int divisor, int maxiter, double tol, const double *V0, int64_t ldv0,
+                 int64_t v0_stride, double warm_lambda, int opt_dim, double *corr, double *nzero_x, double *nzero_y, int *converged,
+                 int *iters, int *warm_iters, double *best_lambda1, double *best_lambda2, double *best_corr, double *xpred, double *ypred);
+
 #ifdef __cplusplus
 }
 #endif

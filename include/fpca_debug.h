@@ -73,6 +73,11 @@ int fpca_debug_k4_bench(fpca_ctx *ctx, int b, int nq, int reps, double *ms_gram,
  * involved): F = r2 / (1 - r2) (n - k - 1) / k and P = upper tail of F(k, n - k - 1) at F = I_{1 - r2}((n - k - 1) / 2, k / 2).
  * FPCA_EINVAL unless k >= 1 and n >= k + 2. */
 int fpca_debug_f_sf(double r2, uint64_t n, int k, double *F, double *P);
+/* diagnostic (tests, scripts/cv_scca_measure.py): the one pass of fpca_scca_cv over the packed stream.  fold[N] in 0 .. nfolds - 1
+ * (2 <= nfolds <= 64); counts (may be NULL): uint32 [nfolds][P_g][3], the samples of each fold with dosage 0, 1, 2 (the missing calls
+ * are the fold's size minus the three); mean_sd (may be NULL): P_g x 2 like fpca_stats, the mean / sd over the samples OUTSIDE fold
+ * which_fold as fpca_scca_cv installs them for that fold.  The context is not changed. */
+int fpca_debug_fold_stats(fpca_ctx *ctx, const uint8_t *fold, int nfolds, uint32_t *counts, int which_fold, double *mean_sd);
 
 #ifdef __cplusplus
 }
