@@ -118,6 +118,14 @@ struct fpca_ctx {
    bool i8_k2_only = false;
    uint8_t *d_packedT = nullptr;
    size_t pitchT = 0;
+   // The copies only the int8 GEMMs stream are BAND-TILED (kernels.hpp packed_piece_offset: every 128-byte line of the packed stream
+   // crosses L2 -> L1 once instead of twice): the sample-major copy, and d_packedK2, a third copy -- the SNP-major matrix in that
+   // layout, same pitch -- that the G.M-alone K2 launches read.  d_packed itself stays row-major for everything else (statistics, the
+   // fp64 / fp32 kernels, downloads, UCCA / SCCA, the two-matrix K2 kernels, the hybrid route's row shuffles).  The third copy is
+   // optional: without it K2 runs the row-major kernel, same results.
+   bool i8_tiled = false;        // d_packedT is band-tiled
+   uint8_t *d_packedK2 = nullptr;
+   bool k2_copy_failed = false;  // it did not fit (or was given back to make room): not tried again
    double *d_inv_sd = nullptr, *d_mu_inv_sd = nullptr, *d_i8w = nullptr;
    int8_t *d_Qb = nullptr, *d_Qg = nullptr, *d_Qm = nullptr;
    int i8_nsc = 0; // rows currently allocated (and zero-padded) in the Q buffers
@@ -245,6 +253,7 @@ struct PreSliced {
 };
 // T = X' B on slices of B (K2 stage); chain: the combine also leaves the column maxima of the two K3 operands
 void xt_i8(fpca_ctx *c, const double *dB, int b, hipStream_t s, bool chain, hipEvent_t *gev = nullptr, const PreSliced *pre = nullptr);
+void drop_k2_copy(fpca_ctx *c, const char *why); // frees the optional band-tiled SNP-major copy (one line on stderr)
 // Y = X T on slices of T/sd and mean T/sd (K3 stage), rows [r0, r1) of Y (r1 = 0: all)
 void x_i8(fpca_ctx *c, int b, double *dY, hipStream_t s, bool have_max, bool do_slice = true, uint64_t r0 = 0, uint64_t r1 = 0,
           hipEvent_t *gev = nullptr);

@@ -116,6 +116,17 @@ void i8_slice_rows(const double *V, uint64_t rows, int b, int S, const SliceOp &
 void i8_unpack_slices(const int8_t *Qrm, uint64_t rows_pad, int b, int S, const SliceOp &op, hipStream_t stream, uint64_t rows_valid = 0,
                       float *copy32 = nullptr, double *copy64 = nullptr);
 void i8_dequant_rows(const int8_t *Qrm, uint64_t rows, int b, int S, const SliceOp &op, float *copy32, double *copy64, hipStream_t stream);
+// Band-tiled layout of a packed copy that only the int8 GEMM streams (the sample-major copy, and the SNP-major copy made for K2).
+// Size, pitch and the offset of a band of 32 rows (32 * pitch bytes) are those of the row-major layout; inside a band the 32 rows x
+// 64 bytes of chunk c (256 codes per row) are 2 KB contiguous, ordered so that the 16-byte piece lane (row i, k-half kh) of the
+// GEMM wants as its h-th load sits at (h * 64 + kh * 32 + i) * 16: one global_load_dwordx4 of a wave reads 1 KB = 8 whole lines.
+// Byte offset of the 16-byte piece q of row r (piece q = bytes [16 q, 16 q + 16) of the record; pitch a multiple of 64):
+__host__ __device__ inline size_t packed_piece_offset(uint64_t r, uint64_t q, size_t pitch, bool tiled)
+{
+   if (!tiled) return (size_t)(r * pitch + q * 16);
+   const uint64_t c = q >> 2, kh = (q >> 1) & 1, h = q & 1;
+   return (size_t)((r >> 5) * 32 * pitch + c * 2048 + (h * 64 + kh * 32 + (r & 31)) * 16);
+}
 int gemm_i8_nsc_pad(int S, int b); // rows of a Q operand: S*b rounded up to the 256-column workgroup tile
 size_t gemm_i8_workspace_doubles(uint64_t rows_pad, uint64_t k_pad, int S, int b, bool two);
 // out[rows_pad][b] = recombined ( (G.M) Qg' , M Qm' ); mean/sd non-null: K2 flavour (per-row standardisation)
@@ -124,7 +135,8 @@ void gemm_i8(const uint8_t *packed, size_t pitch, const int8_t *Qg, const int8_t
              uint64_t rows_valid, int mode /* 0 full, 1 skip E blocks without a missing genotype, 2 G.M alone */,
              const double *eplane /* with mode 2: E'Q [rows_pad][b] from sparse_rows_sum, or null if nothing is missing */, int b, int S,
              const SliceOp *next_ops, hipStream_t stream, hipEvent_t *gemm_events = nullptr, hipEvent_t before_combine = nullptr,
-             bool e_only = false /* mode 2 only: multiply the missing-indicator matrix E instead of G.M; out = E Q */);
+             bool e_only = false /* mode 2 only: multiply the missing-indicator matrix E instead of G.M; out = E Q */,
+             bool tiled = false /* `packed` is in the band-tiled layout (two-matrix and G.M-alone kernels) */);
 // the hybrid missing-indicator route's row shuffles (kernels_i8.hip)
 void gather_packed_rows(const uint8_t *src, size_t pitch, const uint32_t *idx, uint32_t nidx, uint32_t rows_out, uint8_t *dst, hipStream_t stream);
 void patch_missing_rows(uint8_t *packed, size_t pitch, const uint32_t *idx, uint32_t nidx, hipStream_t stream);
@@ -132,8 +144,10 @@ void scatter_packed_rows(const uint8_t *src, size_t pitch, const uint32_t *idx, 
 void gather_scaled_rows(const double *V, const double *scale, const uint32_t *idx, uint32_t nidx, uint64_t rows_out, int b, double *dst, hipStream_t stream);
 void scatter_rows(const double *src, const uint32_t *idx, uint32_t nidx, int b, double *dst, hipStream_t stream);
 // index lists of the missing calls of 2-bit records (positions < ncols), and the gather-sum over them
-void count_missing(const uint8_t *packed, size_t pitch, uint64_t ncols, uint64_t nrec, uint32_t *cnt, hipStream_t stream);
-void fill_missing(const uint8_t *packed, size_t pitch, uint64_t ncols, uint64_t nrec, const uint32_t *ptr, uint32_t *idx, hipStream_t stream);
+// (tiled: the records are in the band-tiled layout)
+void count_missing(const uint8_t *packed, size_t pitch, uint64_t ncols, uint64_t nrec, uint32_t *cnt, hipStream_t stream, bool tiled = false);
+void fill_missing(const uint8_t *packed, size_t pitch, uint64_t ncols, uint64_t nrec, const uint32_t *ptr, uint32_t *idx, hipStream_t stream,
+                  bool tiled = false);
 void sparse_rows_sum(const uint32_t *ptr, const uint32_t *idx, const double *V, const double *rowscale, int b, uint64_t nrec,
                      uint64_t rows_out, double *out, hipStream_t stream, const double *init = nullptr /* [rows_out][b] added to the sums */,
                      bool short_lists = false /* many short lists (per sample): the batched index reads */,
@@ -145,7 +159,9 @@ void sparse_rows_sum_f32(const uint32_t *ptr, const uint32_t *idx, const float *
 void i8_rowscales(const double *mean, const double *sd, uint64_t P_g, uint64_t P_pad, double *inv_sd, double *mu_inv_sd,
                   hipStream_t stream);
 void transpose_packed(const uint8_t *in, size_t pitch_in, uint64_t N_pad, uint64_t P_pad, uint8_t *out, size_t pitch_out,
-                      hipStream_t stream);
+                      hipStream_t stream, bool tiled = false /* write the band-tiled layout */);
+// out = the band-tiled arrangement of the row-major records in[rows][pitch] (rows a multiple of 32, pitch of 64)
+void tile_packed(const uint8_t *in, size_t pitch, uint64_t rows, uint8_t *out, hipStream_t stream);
 double mfma_i8_peak_tops(int waves_per_simd, int iters, uint32_t fill, hipStream_t stream);
 void mfma_i8_probe(const int8_t *A, const int8_t *Bt, int *D, hipStream_t stream);
 

@@ -539,9 +539,14 @@ enum { I8_FULL = 0, I8_SKIP_EMPTY = 1, I8_NO_MISSING = 2 };
 // 32 rows x 2 k-halves each) are regrouped by v_permlane16_swap into two 16-row x 64-k operands, the slice-column operand is
 // one ds_read_b128 per lane with the matching (k-half, k-step) -> quarter order.  A bare stream of the two mixes
 // (profiles/r03_mfma_mix_probe.txt): 3280 -> 3720 useful TOP/s.
-template <bool TWO_, int MT_, int NT_, int WR_, int WC_, int KC_, int G_, int MODE_ = I8_FULL, bool HALF_ = false>
+// TILED: `packed` is in the band-tiled layout (kernels.hpp packed_piece_offset): the two 16-byte pieces of a lane are two loads in
+// which the wave reads 1 KB contiguous each -- every 128-byte line of the packed stream is requested once.  On the row-major layout
+// a load touches 32 lines and uses 32 bytes of each, and the other half of every line is wanted one chunk later, after the line has
+// left the 32 KB L1: each packed byte crosses L2 -> L1 twice.  Same registers, same order of loads and waits.
+template <bool TWO_, int MT_, int NT_, int WR_, int WC_, int KC_, int G_, int MODE_ = I8_FULL, bool HALF_ = false, bool TILED_ = false>
 struct I8Cfg {
-   static constexpr bool TWO = TWO_, HALF = HALF_;
+   static constexpr bool TWO = TWO_, HALF = HALF_, TILED = TILED_;
+   static_assert(!TILED || KC_ == 256, "the band-tiled layout is cut in chunks of 256 codes");
    static constexpr int MT = MT_, NT = NT_, WR = WR_, WC = WC_, KC = KC_, G = G_, NQ = TWO ? 2 : 1, MODE = MODE_;
    static constexpr int MATS = MODE == I8_NO_MISSING ? 1 : 2;
    static constexpr int NTF = HALF ? NT - 1 : NT;       // full 32-column tiles
@@ -660,7 +665,9 @@ __global__ __launch_bounds__(256, 1) void k_gemm_i8(const uint8_t *__restrict__ 
    // packed words: lane (li, kh) of wave row wr decodes rows wr*32*MT + 32 m + li, k = (KC/2) kh + 16 ks .. of the chunk
    uint32_t pvoff[MT];
 #pragma unroll
-   for (int m = 0; m < MT; m++) pvoff[m] = (uint32_t)((wr * 32 * MT + 32 * m + li) * pitch + kh * (KC / 8));
+   for (int m = 0; m < MT; m++)
+      pvoff[m] = C::TILED ? (uint32_t)((wr * MT + m) * 32 * pitch + lane * 16) // band of the m-tile, piece (kh, li) of a 1 KB half block
+                          : (uint32_t)((wr * 32 * MT + 32 * m + li) * pitch + kh * (KC / 8));
    const uint8_t *prow = packed + row0 * pitch;
    const uint32_t aQ0 = lds_base + (uint32_t)(wc * 32 * NT + li) * LDQ + kh * (KC / 2);
    // HALF: lane (column j = lane & 15, quarter qd = lane >> 4) of the 16x16x64 operand reads k-half qd >> 1 of k-step 2 kp + (qd & 1)
@@ -675,11 +682,11 @@ __global__ __launch_bounds__(256, 1) void k_gemm_i8(const uint8_t *__restrict__ 
       qreg[r] = gload16<0>(sb, qvoff);
    };
    auto issue_p = [&](u4(&dst)[MT][PW], int cc) {
-      const uint8_t *pb = prow + (size_t)cc * (KC / 4);
+      const uint8_t *pb = prow + (size_t)cc * (C::TILED ? 2048 : KC / 4);
 #pragma unroll
       for (int m = 0; m < MT; m++) {
          dst[m][0] = gload16<0>(pb, pvoff[m]);
-         if constexpr (PW == 2) dst[m][1] = gload16<16>(pb, pvoff[m]);
+         if constexpr (PW == 2) dst[m][1] = gload16<(C::TILED ? 1024 : 16)>(pb, pvoff[m]);
       }
    };
    auto store_q = [&](auto rr, unsigned char *st) {
@@ -1115,9 +1122,12 @@ void gemm_i8(const uint8_t *packed, size_t pitch, const int8_t *Qg, const int8_t
              int S, const SliceOp *next_ops /* null, or the two operands whose column maxima the combine should leave */,
              hipStream_t stream, hipEvent_t *gemm_events /* null, or 2 events recorded around the GEMM kernel itself */,
              hipEvent_t before_combine /* null, or an event the combine must wait for (eplane produced on another stream) */,
-             bool e_only /* mode 2 only: the missing-indicator matrix E alone, out = E Q (no statistics, no column sums) */)
+             bool e_only /* mode 2 only: the missing-indicator matrix E alone, out = E Q (no statistics, no column sums) */,
+             bool tiled /* `packed` is band-tiled: the two-matrix kernels and the G.M-alone ones have an instance for it */)
 {
    const bool two = (Qg != Qm);
+   if (tiled && !two && mode != I8_NO_MISSING) throw Error(-1, "gemm_i8: the one-operand kernels of both matrices read the row-major layout only");
+   if (tiled && (pitch % 64 || k_pad > 4 * pitch)) throw Error(-1, "gemm_i8: a band-tiled copy has whole 64-byte chunks per row");
    if (e_only && (mode != I8_NO_MISSING || two)) throw Error(-1, "gemm_i8: e_only goes with the one-matrix kernel");
    const I8Shape sh = i8_shape(S, b, two, mode);
    const int bw = i8_bw(b); // Q holds gemm_i8_nsc_pad(S, b) rows; rows >= S*b are zero and carry zero weights
@@ -1126,11 +1136,12 @@ void gemm_i8(const uint8_t *packed, size_t pitch, const int8_t *Qg, const int8_t
 #define FPCA_I8_ARGS pl, stream, packed, pitch, Qg, Qm, k_pad, wg, wm, bw, ws, rows_pad, chunks_total, sh.zb, (e_only ? 0x00000100u : 0x00010002u)
    if (gemm_events) (void)hipEventRecord(gemm_events[0], stream);
    if (two && mode == I8_NO_MISSING) throw Error(-1, "gemm_i8: without missing genotypes both matrices share one operand (pass Qm == Qg)");
-#define FPCA_I8_K3(NT_, MODE_) launch_i8<I8Cfg<true, 2, NT_, 4, 1, 256, 1, MODE_>>(FPCA_I8_ARGS)
+// (TL: the instance for the band-tiled layout -- every kernel that reads the sample-major copy, and the G.M-alone K2 kernels)
+#define FPCA_I8_K3(NT_, MODE_) launch_i8<I8Cfg<true, 2, NT_, 4, 1, 256, 1, MODE_, false, TL>>(FPCA_I8_ARGS)
 // one matrix, or both in a narrow column block (<= 3 tiles): 64-row waves; both from 4 tiles up: 32-row waves, the tiles in 2 groups
 #define FPCA_I8_K2(NT_, MODE_)                                                                                               \
    launch_i8<I8Cfg<false, (MODE_ == I8_NO_MISSING || NT_ <= 3 ? 2 : 1), NT_, 4, 1, 256, (MODE_ == I8_NO_MISSING || NT_ <= 3 ? 1 : 2), \
-                   MODE_>>(FPCA_I8_ARGS)
+                   MODE_, false, TL>>(FPCA_I8_ARGS)
 #define FPCA_I8_K3_NT(MODE_)                       \
    switch (sh.nt) {                                \
    case 2: FPCA_I8_K3(2, MODE_); break;            \
@@ -1147,27 +1158,36 @@ void gemm_i8(const uint8_t *packed, size_t pitch, const int8_t *Qg, const int8_t
    case 7: FPCA_I8_K2(7, MODE_); break;            \
    default: FPCA_I8_K2(8, MODE_); break;           \
    }
-   if (two) {
-      if (sh.half)
-         launch_i8<I8Cfg<true, 2, 4, 4, 1, 256, 1, I8_FULL, true>>(FPCA_I8_ARGS);
-      else if (mode == I8_SKIP_EMPTY)
-         FPCA_I8_K3_NT(I8_SKIP_EMPTY)
-      else
-         FPCA_I8_K3_NT(I8_FULL)
-   } else if (mode == I8_NO_MISSING) {
-      if (sh.half && sh.nt == 2)
-         launch_i8<I8Cfg<false, 2, 2, 4, 1, 256, 1, I8_NO_MISSING, true>>(FPCA_I8_ARGS);
-      else if (sh.half)
-         launch_i8<I8Cfg<false, 2, 4, 4, 1, 256, 1, I8_NO_MISSING, true>>(FPCA_I8_ARGS);
-      else
-         FPCA_I8_K2_NT(I8_NO_MISSING)
-   } else if (mode == I8_SKIP_EMPTY) {
-      FPCA_I8_K2_NT(I8_SKIP_EMPTY)
-   } else if (sh.half) {
-      launch_i8<I8Cfg<false, 2, 4, 4, 1, 256, 1, I8_FULL, true>>(FPCA_I8_ARGS);
-   } else {
-      FPCA_I8_K2_NT(I8_FULL)
-   }
+   auto run = [&](auto tl) {
+      constexpr bool TL = decltype(tl)::value;
+      if (two) {
+         if (sh.half)
+            launch_i8<I8Cfg<true, 2, 4, 4, 1, 256, 1, I8_FULL, true, TL>>(FPCA_I8_ARGS);
+         else if (mode == I8_SKIP_EMPTY)
+            FPCA_I8_K3_NT(I8_SKIP_EMPTY)
+         else
+            FPCA_I8_K3_NT(I8_FULL)
+      } else if (mode == I8_NO_MISSING) {
+         if (sh.half && sh.nt == 2)
+            launch_i8<I8Cfg<false, 2, 2, 4, 1, 256, 1, I8_NO_MISSING, true, TL>>(FPCA_I8_ARGS);
+         else if (sh.half)
+            launch_i8<I8Cfg<false, 2, 4, 4, 1, 256, 1, I8_NO_MISSING, true, TL>>(FPCA_I8_ARGS);
+         else
+            FPCA_I8_K2_NT(I8_NO_MISSING)
+      } else if constexpr (!TL) { // both matrices against one operand (K2, dense missing-indicator routes): row-major only
+         if (mode == I8_SKIP_EMPTY) {
+            FPCA_I8_K2_NT(I8_SKIP_EMPTY)
+         } else if (sh.half) {
+            launch_i8<I8Cfg<false, 2, 4, 4, 1, 256, 1, I8_FULL, true>>(FPCA_I8_ARGS);
+         } else {
+            FPCA_I8_K2_NT(I8_FULL)
+         }
+      }
+   };
+   if (tiled)
+      run(std::true_type{});
+   else
+      run(std::false_type{});
 #undef FPCA_I8_K2_NT
 #undef FPCA_I8_K3_NT
 #undef FPCA_I8_K2
@@ -1214,23 +1234,25 @@ void i8_rowscales(const double *mean, const double *sd, uint64_t P_g, uint64_t P
 // route took 8-9 -- while the int8 GEMM multiplies G.M alone with the one-matrix kernel.
 
 // missing calls of each 2-bit record among its first `ncols` codes
+// (tiled: the records are in the band-tiled layout -- byte j of a record sits in its 16-byte piece j / 16)
 __global__ __launch_bounds__(256) void k_count_missing(const uint8_t *__restrict__ packed, size_t pitch, uint64_t ncols,
-                                                        uint32_t *__restrict__ cnt)
+                                                        uint32_t *__restrict__ cnt, bool tiled)
 {
-   const uint8_t *row = packed + (uint64_t)blockIdx.x * pitch;
+   const uint64_t rec = blockIdx.x;
+   auto byte_at = [&](uint64_t j) { return packed + packed_piece_offset(rec, j >> 4, pitch, tiled) + (j & 15); };
    const uint64_t nbytes = (ncols + 3) / 4, nw = nbytes / 4;
    uint32_t n = 0;
    for (uint64_t i = threadIdx.x; i < nw; i += 256) {
-      const uint32_t w = reinterpret_cast<const uint32_t *>(row)[i];
+      const uint32_t w = *reinterpret_cast<const uint32_t *>(byte_at(4 * i));
       n += __popc(w & ~(w >> 1) & 0x55555555u);
    }
    for (uint64_t i = nw * 4 + threadIdx.x; i < nbytes; i += 256) {
-      const uint32_t w = row[i];
+      const uint32_t w = *byte_at(i);
       n += __popc(w & ~(w >> 1) & 0x55u);
    }
    // codes beyond ncols in the last byte
    if (threadIdx.x == 0 && (ncols & 3)) {
-      const uint32_t w = row[nbytes - 1] >> (2 * (ncols & 3));
+      const uint32_t w = *byte_at(nbytes - 1) >> (2 * (ncols & 3));
       n -= __popc(w & ~(w >> 1) & 0x55u);
    }
    __shared__ uint32_t red[256];
@@ -1248,9 +1270,8 @@ __global__ __launch_bounds__(256) void k_count_missing(const uint8_t *__restrict
 // place each thread's hits.  (Rows are 128-byte aligned and padded with "missing" codes up to the pitch, so whole
 // 16-byte pieces can be read; positions >= ncols are masked off.)
 __global__ __launch_bounds__(256) void k_fill_missing(const uint8_t *__restrict__ packed, size_t pitch, uint64_t ncols,
-                                                       const uint32_t *__restrict__ ptr, uint32_t *__restrict__ idx)
+                                                       const uint32_t *__restrict__ ptr, uint32_t *__restrict__ idx, bool tiled)
 {
-   const u4 *row = reinterpret_cast<const u4 *>(packed + (uint64_t)blockIdx.x * pitch);
    const uint64_t nq = (ncols + 63) / 64; // 16-byte pieces holding valid codes
    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
    __shared__ uint32_t wsum[4];
@@ -1261,7 +1282,7 @@ __global__ __launch_bounds__(256) void k_fill_missing(const uint8_t *__restrict_
       const uint64_t q = q0 + threadIdx.x;
       uint32_t m[4] = {0u, 0u, 0u, 0u};
       if (q < nq) {
-         const u4 x = row[q];
+         const u4 x = *reinterpret_cast<const u4 *>(packed + packed_piece_offset(blockIdx.x, q, pitch, tiled));
 #pragma unroll
          for (int k = 0; k < 4; k++) {
             m[k] = x[k] & ~(x[k] >> 1) & 0x55555555u;
@@ -1302,17 +1323,18 @@ __global__ __launch_bounds__(256) void k_fill_missing(const uint8_t *__restrict_
    }
 }
 
-void count_missing(const uint8_t *packed, size_t pitch, uint64_t ncols, uint64_t nrec, uint32_t *cnt, hipStream_t stream)
+void count_missing(const uint8_t *packed, size_t pitch, uint64_t ncols, uint64_t nrec, uint32_t *cnt, hipStream_t stream, bool tiled)
 {
    if (!nrec) return;
-   hipLaunchKernelGGL(k_count_missing, dim3((unsigned)nrec), dim3(256), 0, stream, packed, pitch, ncols, cnt);
+   hipLaunchKernelGGL(k_count_missing, dim3((unsigned)nrec), dim3(256), 0, stream, packed, pitch, ncols, cnt, tiled);
    HIP_CHECK_LAUNCH();
 }
 
-void fill_missing(const uint8_t *packed, size_t pitch, uint64_t ncols, uint64_t nrec, const uint32_t *ptr, uint32_t *idx, hipStream_t stream)
+void fill_missing(const uint8_t *packed, size_t pitch, uint64_t ncols, uint64_t nrec, const uint32_t *ptr, uint32_t *idx, hipStream_t stream,
+                  bool tiled)
 {
    if (!nrec) return;
-   hipLaunchKernelGGL(k_fill_missing, dim3((unsigned)nrec), dim3(256), 0, stream, packed, pitch, ncols, ptr, idx);
+   hipLaunchKernelGGL(k_fill_missing, dim3((unsigned)nrec), dim3(256), 0, stream, packed, pitch, ncols, ptr, idx, tiled);
    HIP_CHECK_LAUNCH();
 }
 
@@ -1587,7 +1609,9 @@ void scatter_rows(const double *src, const uint32_t *idx, uint32_t nidx, int b, 
 //   tile = 256 SNPs x 256 samples.  A thread loads the 16 x 16 block (16 SNP rows, one dword = 16 samples each; the 16
 //   lanes of a sample-word run read 64 contiguous bytes of a row), transposes it in registers with the four
 //   butterfly stages of a bit-matrix transpose on 2-bit elements, and the 256 blocks are regrouped through LDS so that
-//   every thread stores 64 contiguous bytes (256 SNPs) of one sample row.
+//   every thread stores 64 contiguous bytes (256 SNPs) of one sample row -- or, band-tiled (TILED, kernels.hpp
+//   packed_piece_offset), the four 16-byte pieces of that (row, chunk): the workgroup's stores are eight whole 2 KB blocks.
+template <bool TILED>
 __global__ __launch_bounds__(256) void k_transpose_packed(const uint8_t *__restrict__ in, size_t pitch_in, uint8_t *__restrict__ out,
                                                            size_t pitch_out)
 {
@@ -1616,18 +1640,43 @@ __global__ __launch_bounds__(256) void k_transpose_packed(const uint8_t *__restr
    __syncthreads();
    {
       const int r = threadIdx.x;
-      u4 *dst = reinterpret_cast<u4 *>(out + (smp0 + r) * pitch_out + snp0 / 4);
 #pragma unroll
-      for (int q = 0; q < 4; q++) dst[q] = (u4){tile[r][4 * q], tile[r][4 * q + 1], tile[r][4 * q + 2], tile[r][4 * q + 3]};
+      for (int q = 0; q < 4; q++)
+         *reinterpret_cast<u4 *>(out + packed_piece_offset(smp0 + r, snp0 / 64 + q, pitch_out, TILED)) =
+            (u4){tile[r][4 * q], tile[r][4 * q + 1], tile[r][4 * q + 2], tile[r][4 * q + 3]};
    }
 }
 
 void transpose_packed(const uint8_t *in, size_t pitch_in, uint64_t N_pad, uint64_t P_pad, uint8_t *out, size_t pitch_out,
-                      hipStream_t stream)
+                      hipStream_t stream, bool tiled)
 {
    if (N_pad % 256 || P_pad % 256) throw Error(-1, "transpose_packed: padded sizes must be multiples of 256");
+   if (tiled && pitch_out % 64) throw Error(-1, "transpose_packed: a band-tiled copy has whole 64-byte chunks per row");
    dim3 grid((unsigned)(P_pad / 256), (unsigned)(N_pad / 256));
-   hipLaunchKernelGGL(k_transpose_packed, grid, dim3(256), 0, stream, in, pitch_in, out, pitch_out);
+   if (tiled)
+      hipLaunchKernelGGL(k_transpose_packed<true>, grid, dim3(256), 0, stream, in, pitch_in, out, pitch_out);
+   else
+      hipLaunchKernelGGL(k_transpose_packed<false>, grid, dim3(256), 0, stream, in, pitch_in, out, pitch_out);
+   HIP_CHECK_LAUNCH();
+}
+
+// the band-tiled arrangement of row-major records (the copy K2 streams): a thread moves the four 16-byte pieces of one (row, chunk);
+// a wave reads 64 B of 64 rows and writes two whole 2 KB blocks
+__global__ __launch_bounds__(256) void k_tile_packed(const uint8_t *__restrict__ in, size_t pitch, uint8_t *__restrict__ out)
+{
+   const uint64_t r = (uint64_t)blockIdx.y * 256 + threadIdx.x, c = blockIdx.x;
+   u4 v[4];
+#pragma unroll
+   for (int q = 0; q < 4; q++) v[q] = *reinterpret_cast<const u4 *>(in + packed_piece_offset(r, 4 * c + q, pitch, false));
+#pragma unroll
+   for (int q = 0; q < 4; q++) *reinterpret_cast<u4 *>(out + packed_piece_offset(r, 4 * c + q, pitch, true)) = v[q];
+}
+
+void tile_packed(const uint8_t *in, size_t pitch, uint64_t rows, uint8_t *out, hipStream_t stream)
+{
+   if (rows % 256 || pitch % 64) throw Error(-1, "tile_packed: rows in multiples of 256, whole 64-byte chunks per row");
+   if (!rows) return;
+   hipLaunchKernelGGL(k_tile_packed, dim3((unsigned)(pitch / 64), (unsigned)(rows / 256)), dim3(256), 0, stream, in, pitch, out);
    HIP_CHECK_LAUNCH();
 }
 

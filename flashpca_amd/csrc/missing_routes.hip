@@ -25,12 +25,56 @@ constexpr double SPARSE_BREAK_EVEN = 0.005; // missing-call rate at which the ga
 static void hybrid_classify(fpca_ctx *c);
 static void ensure_i8_alloc(fpca_ctx *c, int b);
 
+// 0 (test builds): every packed copy row-major, as before the band tiling -- one binary runs both layouts
+static bool i8_want_tiled()
+{
+   const char *env = FPCA_TEST_ENV("FPCA_I8_TILED");
+   return !env || atoi(env) != 0;
+}
+
+void drop_k2_copy(fpca_ctx *c, const char *why)
+{
+   if (c->d_packedK2) {
+      (void)hipStreamSynchronize(c->stream);
+      (void)hipFree(c->d_packedK2);
+      c->d_packedK2 = nullptr;
+   }
+   c->k2_copy_failed = true;
+   std::fprintf(stderr, "[fpca] no band-tiled copy of the SNP-major matrix (%.1f GiB; %s): X'B streams the row-major matrix, same results\n",
+                (double)c->pitch * (double)c->P_pad / (1024.0 * 1024.0 * 1024.0), why);
+}
+
+// The third copy (ctx.hpp d_packedK2), made once from the plain SNP-major matrix.  Taken only where as much again stays free behind
+// it: the index lists, the wider blocks' operands and the eigensolver's basis are still to come, and none of them may fail for it.
+static void ensure_k2_copy(fpca_ctx *c)
+{
+   if (c->d_packedK2 || c->k2_copy_failed || !c->i8_tiled) return;
+   const size_t bytes = c->pitch * c->P_pad;
+   size_t fr = 0, tot = 0;
+   if (FPCA_TEST_ENV("FPCA_DEBUG_I8_NOK2COPY")) return drop_k2_copy(c, "FPCA_DEBUG_I8_NOK2COPY is set"); // exercises the row-major K2
+   if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < 2 * bytes) return drop_k2_copy(c, "less than twice its size is free");
+   if (hipMalloc(&c->d_packedK2, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      c->d_packedK2 = nullptr;
+      return drop_k2_copy(c, "out of device memory");
+   }
+   kern::tile_packed(c->d_packed, c->pitch, c->P_pad, c->d_packedK2, c->stream);
+}
+
 // true: the int8 path is ready for blocks of width b.  false (FPCA_ACCUM_AUTO only): its extra buffers did not fit, the
 // context has been switched to the fp64 kernels for good.
 bool ensure_i8(fpca_ctx *c, int b)
 {
    try {
-      ensure_i8_alloc(c, b);
+      try {
+         ensure_i8_alloc(c, b);
+      } catch (const Error &e) {
+         // the optional third copy must never be what pushes the mode's own buffers out of memory: give it back and try once more
+         if (e.code != FPCA_ENOMEM || !c->d_packedK2) throw;
+         (void)hipGetLastError();
+         drop_k2_copy(c, e.what());
+         ensure_i8_alloc(c, b);
+      }
       return true;
    } catch (const Error &e) {
       if (!c->i8_auto && e.code == FPCA_ENOMEM) { // asked for explicitly: no silent change of arithmetic -- say what would fit
@@ -48,7 +92,7 @@ bool ensure_i8(fpca_ctx *c, int b)
       if (!c->i8_auto || e.code != FPCA_ENOMEM) throw; // only "does not fit"; a kernel or launch failure is not masked
       (void)hipGetLastError();
       std::fprintf(stderr, "[fpca] exact-integer mode needs more device memory than is free (%s); using the fp64 kernels\n", e.what());
-      void **ptrs[] = {(void **)&c->d_packedT, (void **)&c->d_Qb, (void **)&c->d_Qg, (void **)&c->d_Qm, (void **)&c->d_i8ws};
+      void **ptrs[] = {(void **)&c->d_packedT, (void **)&c->d_packedK2, (void **)&c->d_Qb, (void **)&c->d_Qg, (void **)&c->d_Qm, (void **)&c->d_i8ws};
       for (void **p : ptrs)
          if (*p) {
             (void)hipFree(*p);
@@ -81,6 +125,7 @@ void ensure_i8_alloc(fpca_ctx *c, int b)
       try {
          if (FPCA_TEST_ENV("FPCA_DEBUG_I8_NOCOPY")) throw Error(FPCA_ENOMEM, "FPCA_DEBUG_I8_NOCOPY is set"); // exercises the K2-only state
          HIP_ALLOC(hipMalloc(&c->d_packedT, c->pitchT * c->N_pad));
+         c->i8_tiled = i8_want_tiled();
       } catch (const Error &e) {
          if (!c->i8_auto || e.code != FPCA_ENOMEM) throw;
          (void)hipGetLastError();
@@ -127,7 +172,7 @@ void ensure_i8_alloc(fpca_ctx *c, int b)
             kern::patch_missing_rows(c->d_packed, c->pitch, c->d_hyb_idx, c->hyb_n, s);
             patched = true;
          }
-         kern::transpose_packed(c->d_packed, c->pitch, c->N_pad, c->P_pad, c->d_packedT, c->pitchT, s);
+         kern::transpose_packed(c->d_packed, c->pitch, c->N_pad, c->P_pad, c->d_packedT, c->pitchT, s, c->i8_tiled);
          if (hyb) {
             kern::scatter_packed_rows(c->d_packedE, c->pitch, c->d_hyb_idx, c->hyb_n, c->d_packed, s);
             patched = false;
@@ -148,6 +193,7 @@ void ensure_i8_alloc(fpca_ctx *c, int b)
          c->hyb_failed = true;
          throw;
       }
+      ensure_k2_copy(c); // (the SNP-major matrix is the plain one again here)
       c->i8_transposed = true;
    }
    if (!c->i8_scales_done) {
@@ -349,7 +395,7 @@ void ensure_sparse(fpca_ctx *c, int b)
    }
    uint32_t *d_cnt = nullptr;
    HIP_ALLOC(hipMalloc(&d_cnt, c->N * sizeof(uint32_t)));
-   kern::count_missing(c->d_packedT, c->pitchT, c->P_g, c->N, d_cnt, s);
+   kern::count_missing(c->d_packedT, c->pitchT, c->P_g, c->N, d_cnt, s, c->i8_tiled);
    std::vector<uint32_t> cnt(c->N);
    HIP_CHECK(hipMemcpyAsync(cnt.data(), d_cnt, c->N * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
    HIP_CHECK(hipStreamSynchronize(s));
@@ -360,7 +406,7 @@ void ensure_sparse(fpca_ctx *c, int b)
    HIP_ALLOC(hipMalloc(&c->d_smp_ptr, (c->N + 1) * sizeof(uint32_t)));
    HIP_ALLOC(hipMalloc(&c->d_smp_idx, std::max<uint64_t>(nnz, 1) * sizeof(uint32_t)));
    HIP_CHECK(hipMemcpyAsync(c->d_smp_ptr, ptr.data(), (c->N + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-   kern::fill_missing(c->d_packedT, c->pitchT, c->P_g, c->N, c->d_smp_ptr, c->d_smp_idx, s);
+   kern::fill_missing(c->d_packedT, c->pitchT, c->P_g, c->N, c->d_smp_ptr, c->d_smp_idx, s, c->i8_tiled);
    HIP_CHECK(hipStreamSynchronize(s));
    c->sparse_ready = true;
 }
@@ -371,7 +417,7 @@ void ensure_sparse(fpca_ctx *c, int b)
 void plain_view(fpca_ctx *c)
 {
    if (!c->hyb_view) return;
-   kern::transpose_packed(c->d_packed, c->pitch, c->N_pad, c->P_pad, c->d_packedT, c->pitchT, c->stream);
+   kern::transpose_packed(c->d_packed, c->pitch, c->N_pad, c->P_pad, c->d_packedT, c->pitchT, c->stream, c->i8_tiled);
    HIP_CHECK(hipStreamSynchronize(c->stream));
    for (void **q : {(void **)&c->d_snp_ptr, (void **)&c->d_snp_idx, (void **)&c->d_smp_ptr, (void **)&c->d_smp_idx, (void **)&c->d_packedE,
                     (void **)&c->d_packedET, (void **)&c->d_hyb_idx})
@@ -526,8 +572,10 @@ void xt_i8(fpca_ctx *c, const double *dB, int b, hipStream_t s, bool chain, hipE
       eplane = c->d_eplane;
       mode = I8M_NONE;
    }
-   kern::gemm_i8(c->d_packed, c->pitch, c->d_Qb, c->d_Qb, ob.colw, ob.colw, ob.colsum, c->d_mean, c->d_sd, c->d_T, c->d_i8ws, c->P_pad,
-                 c->N_pad, c->P_g, mode, eplane, b, c->cur_S(), chain ? ot : nullptr, s, gev, wait);
+   // (G.M alone: the band-tiled third copy if there is one; the two-matrix kernels read the row-major matrix)
+   const bool k2t = c->d_packedK2 && mode == I8M_NONE;
+   kern::gemm_i8(k2t ? c->d_packedK2 : c->d_packed, c->pitch, c->d_Qb, c->d_Qb, ob.colw, ob.colw, ob.colsum, c->d_mean, c->d_sd, c->d_T, c->d_i8ws, c->P_pad,
+                 c->N_pad, c->P_g, mode, eplane, b, c->cur_S(), chain ? ot : nullptr, s, gev, wait, false, k2t);
 }
 
 // Y = X T : slices of T/sd and mean T/sd (one pass over T) against the sample-major copy, rows [r0, r1) of Y
@@ -587,10 +635,11 @@ void x_i8(fpca_ctx *c, int b, double *dY, hipStream_t s, bool have_max, bool do_
       if (sparse_on_side_stream(c, b)) wait = c->ev_aux_done;
       mode = I8M_NONE;
    }
+   if (c->i8_tiled && r0 % 32) throw Error(-1, "x_i8: a row range of the band-tiled copy starts at a multiple of 32 rows");
    // G.M alone: one operand (Qm is still sliced: its column sums are 1'Qm, and M'Qm = 1'Qm - E'Qm)
    kern::gemm_i8(c->d_packedT + r0 * c->pitchT, c->pitchT, c->d_Qg, mode == I8M_NONE ? c->d_Qg : c->d_Qm, ot[0].colw, ot[1].colw,
                  ot[1].colsum, nullptr, nullptr, dY + r0 * b, c->d_i8ws, r1 - r0, c->P_pad, c->N > r0 ? std::min(c->N - r0, r1 - r0) : 0, mode,
-                 eplane, b, c->cur_S(), nullptr, s, gev, wait);
+                 eplane, b, c->cur_S(), nullptr, s, gev, wait, false, c->i8_tiled);
 }
 
 } // namespace fpca
