@@ -117,6 +117,8 @@ SIGNATURES = {
     "fpca_download_packed": (_I, [_P, _P]),
     "fpca_stats": (_I, [_P, _P, C.POINTER(_D)]),
     "fpca_set_meansd": (_I, [_P, _P]),
+    "fpca_set_sample_mask": (_I, [_P, _P]),
+    "fpca_nkept": (_U64, [_P]),
     "fpca_apply_xxt": (_I, [_P, _P, C.c_int64, _I, _P, C.c_int64]),
     "fpca_apply_xt": (_I, [_P, _P, C.c_int64, _I, _P, C.c_int64]),
     "fpca_apply_x": (_I, [_P, _P, C.c_int64, _I, _P, C.c_int64]),

@@ -126,6 +126,24 @@ class Context:
         m = np.asfortranarray(meansd, dtype=np.float64)
         check(lib().fpca_set_meansd(self.h, _p(m)))
 
+    def set_sample_mask(self, keep):
+        """fpca_set_sample_mask: keep is a boolean array with one entry per sample (True = kept), or None to clear the mask.  While a
+        mask is set, stats() / pca() are those of the kept samples, apply_xt / apply_xxt treat the held-out rows as zero and apply_x
+        computes every row; pca() returns U with zero held-out rows and Px with the held-out samples projected onto the PCs."""
+        if keep is None:
+            check(lib().fpca_set_sample_mask(self.h, None))
+            return
+        keep = np.asarray(keep)
+        if keep.shape != (self.N,):
+            raise ValueError("keep must have one entry per sample (%d), it has shape %s" % (self.N, keep.shape))
+        k8 = np.ascontiguousarray(keep != 0, dtype=np.uint8)
+        check(lib().fpca_set_sample_mask(self.h, _p(k8)))
+
+    @property
+    def nkept(self):
+        """Samples the statistics and pca() run on (fpca_nkept): the kept ones under a mask, else N."""
+        return int(lib().fpca_nkept(self.h))
+
     def set_total_snps(self, P_total):
         check(lib().fpca_set_total_snps(self.h, int(P_total)))
         self.P_total = int(P_total)
@@ -380,12 +398,15 @@ class Context:
 
 
 def flashpca(X, ndim=10, stand="binom2", divisor="p", maxiter=500, tol=1e-6, do_loadings=False, return_scale=True,
-             device=0, verbose=False, accum="auto", **solver_kw):
+             device=0, verbose=False, accum="auto", keep=None, **solver_kw):
     """PCA of a PLINK fileset; mirrors flashpca() of the reference's R package for the PLINK-prefix input
     (flashpcaR/R/flashpca.R:99-204 -> flashpca_plink_internal, flashpcaR/src/flashpca.cpp:96-197).
 
     X: PLINK root name (X.bed / X.bim / X.fam), or a numeric N x P matrix (NaN = missing; the R function's matrix
     input, flashpcaR/src/flashpca.cpp:17-93, which also accepts stand = "sd" / "center" / "none").
+    keep: a boolean array with one entry per sample (PLINK input only): the PCA runs on the kept samples -- values, vectors,
+    projection, loadings, center, scale and pve are what a run on the subset fileset returns, rows in input order -- and the result
+    gains `projection_all` (N x ndim): the kept samples' rows of `projection`, everyone else projected onto the same PCs.
     Returns values, vectors, projection, loadings, center, scale, pve.
     """
     if divisor not in DIVISOR:
@@ -400,9 +421,17 @@ def flashpca(X, ndim=10, stand="binom2", divisor="p", maxiter=500, tol=1e-6, do_
             raise ValueError("stand must be one of %s" % sorted(_lib.STANDARDISE_DENSE))
         ctx = Context.from_dense(np.asarray(X, dtype=np.float64), stand=stand, device=device)
     with ctx:
+        if keep is not None:
+            keep = np.asarray(keep)
+            if keep.shape != (ctx.N,):
+                raise ValueError("keep must have one entry per sample (%d), it has shape %s" % (ctx.N, keep.shape))
+            keep = keep != 0
+            ctx.set_sample_mask(keep)
         r = ctx.pca(ndim=ndim, tol=tol, maxiter=maxiter, div=divisor, do_loadings=do_loadings, verbose=int(verbose),
                     **solver_kw)
     res = dict(values=r["d"], vectors=r["U"], projection=r["Px"], loadings=r["V"], pve=r["pve"], info=r["info"])
+    if keep is not None:
+        res.update(vectors=r["U"][keep], projection=r["Px"][keep], projection_all=r["Px"])
     if return_scale:
         res["center"] = r["meansd"][:, 0]
         res["scale"] = r["meansd"][:, 1]

@@ -331,11 +331,15 @@ int fpca_set_meansd(fpca_ctx *ctx, const double *mean_sd)
       HIP_CHECK(hipSetDevice(ctx->device));
       if (!mean_sd) throw Error(FPCA_EINVAL, "mean_sd is NULL");
       if (ctx->dense) throw Error(FPCA_EINVAL, "preloaded mean/sd applies to packed genotypes only");
+      if (ctx->masked())
+         throw Error(FPCA_EINVAL, "fpca_set_meansd: a sample mask is set (fpca_set_sample_mask), whose statistics are those of the kept samples; "
+                                  "clear the mask first");
       HIP_CHECK(hipMemcpy(ctx->d_mean, mean_sd, ctx->P_g * sizeof(double), hipMemcpyHostToDevice));
       HIP_CHECK(hipMemcpy(ctx->d_sd, mean_sd + ctx->P_g, ctx->P_g * sizeof(double), hipMemcpyHostToDevice));
       kern::lut_from_meansd(ctx->d_mean, ctx->d_sd, ctx->P_g, ctx->d_lut, ctx->stream);
       HIP_CHECK(hipStreamSynchronize(ctx->stream));
       ctx->i8_scales_done = false;
+      ctx->meansd_preloaded = true;
       ctx->stats_done = true; // trace of the preloaded standardisation is not defined by the reference path
       ctx->trace_local = 0;
    });
@@ -370,7 +374,9 @@ int fpca_apply_xxt(fpca_ctx *ctx, const double *B, int64_t ldb, int b, double *Y
          HIP_CHECK(hipMemcpy2DAsync(ctx->d_stage, ctx->N * sizeof(double), B + (size_t)c0 * ldb, (size_t)ldb * sizeof(double),
                                     ctx->N * sizeof(double), nc, hipMemcpyHostToDevice, ctx->stream));
          kern::colmajor_to_block(ctx->d_stage, ctx->N, ctx->N, ctx->N_pad, bw, nc, ctx->d_io_a, ctx->stream);
+         if (ctx->masked()) mask_rows(ctx, ctx->d_io_a, bw, ctx->stream); // X_kept X_kept' B: the held-out rows of B count as zero ...
          apply_xxt_dev(ctx, ctx->d_io_a, bw, ctx->d_io_b, ctx->stream, nullptr);
+         if (ctx->masked()) mask_rows(ctx, ctx->d_io_b, bw, ctx->stream); // ... and those of the result are zero
          kern::block_to_colmajor(ctx->d_io_b, ctx->N, bw, nc, ctx->d_stage, ctx->N, ctx->stream);
          staged_download(ctx, ctx->d_stage, ctx->N, nc, Y + (size_t)c0 * ldy, ldy, nullptr, 0, nullptr); // (synchronises)
       }
@@ -389,6 +395,7 @@ int fpca_apply_xt(fpca_ctx *ctx, const double *B, int64_t ldb, int b, double *T,
          HIP_CHECK(hipMemcpy2DAsync(ctx->d_stage, ctx->N * sizeof(double), B + (size_t)c0 * ldb, (size_t)ldb * sizeof(double),
                                     ctx->N * sizeof(double), nc, hipMemcpyHostToDevice, ctx->stream));
          kern::colmajor_to_block(ctx->d_stage, ctx->N, ctx->N, ctx->N_pad, bw, nc, ctx->d_io_a, ctx->stream);
+         if (ctx->masked()) mask_rows(ctx, ctx->d_io_a, bw, ctx->stream); // X_kept' B_kept
          xt_dev(ctx, ctx->d_io_a, bw, ctx->stream);
          kern::t_to_colmajor(ctx->d_T, ctx->P_g, bw, nc, nullptr, ctx->d_stage, ctx->P_g, ctx->stream);
          staged_download(ctx, ctx->d_stage, ctx->P_g, nc, T + (size_t)c0 * ldt, ldt, nullptr, 0, nullptr); // (synchronises)
@@ -425,7 +432,15 @@ int fpca_apply_xxt_dev(fpca_ctx *ctx, const double *dB, int b, double *dY, void 
       hipEvent_t *ev = nullptr;
       if (ctx->prof_on && ctx->prof_calls++ % ctx->prof_stride == 0 && (size_t)(ctx->prof_used + 1) * 8 <= ctx->prof_ev.size())
          ev = &ctx->prof_ev[(size_t)ctx->prof_used++ * 8];
-      apply_xxt_dev(ctx, dB, b, dY, stream ? (hipStream_t)stream : ctx->stream, ev);
+      hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+      if (ctx->masked()) { // the caller's block is const: its masked copy goes through the operator
+         ensure_io(ctx);
+         HIP_CHECK(hipMemcpyAsync(ctx->d_io_a, dB, (size_t)ctx->N_pad * b * sizeof(double), hipMemcpyDeviceToDevice, s));
+         mask_rows(ctx, ctx->d_io_a, b, s);
+         dB = ctx->d_io_a;
+      }
+      apply_xxt_dev(ctx, dB, b, dY, s, ev);
+      if (ctx->masked()) mask_rows(ctx, dY, b, s);
    });
 }
 
@@ -444,6 +459,7 @@ int fpca_comm_init_rank(fpca_ctx *ctx, int nranks, int rank, const uint8_t id[FP
 {
    return guarded([&] {
       if (!ctx || nranks < 1 || rank < 0 || rank >= nranks) throw Error(FPCA_EINVAL, "bad argument to fpca_comm_init_rank");
+      refuse_shard_while_masked(ctx, "fpca_comm_init_rank");
       HIP_CHECK(hipSetDevice(ctx->device));
       ncclUniqueId u;
       std::memcpy(&u, id, sizeof(u));
@@ -468,6 +484,7 @@ int fpca_comm_init_rank(fpca_ctx *ctx, int nranks, int rank, const uint8_t id[FP
 int fpca_set_allreduce(fpca_ctx *ctx, fpca_allreduce_fn fn, void *user)
 {
    if (!ctx) return FPCA_EINVAL;
+   if (fn && ctx->masked()) return guarded([&] { refuse_shard_while_masked(ctx, "fpca_set_allreduce"); });
    ctx->ar_fn = fn;
    ctx->ar_user = user;
    if (fn) ctx->comm_dead = false; // (a new transport)
@@ -479,6 +496,7 @@ int fpca_set_collectives(fpca_ctx *ctx, fpca_allgather_fn ag, fpca_reducescatter
 {
    return guarded([&] {
       if (!ctx || (ag == nullptr) != (rs == nullptr)) throw Error(FPCA_EINVAL, "bad argument to fpca_set_collectives");
+      if (ag) refuse_shard_while_masked(ctx, "fpca_set_collectives");
       HIP_CHECK(hipSetDevice(ctx->device));
       ctx->ag_fn = ag;
       ctx->rs_fn = rs;
@@ -492,6 +510,7 @@ int fpca_set_collectives(fpca_ctx *ctx, fpca_allgather_fn ag, fpca_reducescatter
 int fpca_set_rank(fpca_ctx *ctx, int nranks, int rank)
 {
    if (!ctx || nranks < 1 || rank < 0 || rank >= nranks) return FPCA_EINVAL;
+   if (nranks > 1 && ctx->masked()) return guarded([&] { refuse_shard_while_masked(ctx, "fpca_set_rank"); });
    ctx->nranks = nranks;
    ctx->rank = rank;
    ctx->rank_known = true;
@@ -570,7 +589,11 @@ int fpca_pca(fpca_ctx *ctx, const fpca_pca_opts *opts, double *U, double *d, dou
       HIP_CHECK(hipSetDevice(ctx->device));
       const int k = opts->ndim;
       // Spectra's requirement nev < ncv = 2 nev + 1 <= n, enforced by the reference CLI (flashpca.cpp:623-633)
-      const uint64_t lim = std::min(ctx->N, ctx->P_total);
+      // A sample mask (fpca_set_sample_mask): the kept-sample problem.  The backend shows the solver n_kept rows, so the divisor n1, the
+      // dimension limit and the small-N route follow from n_kept; U / Px are spread over the caller's N rows afterwards.
+      const bool masked = ctx->masked();
+      const uint64_t Ns = masked ? ctx->n_kept : ctx->N;
+      const uint64_t lim = std::min(Ns, ctx->P_total);
       const uint64_t max_dim = lim >= 1 ? (lim - 1) / 2 : 0;
       if (k < 1 || (uint64_t)k > max_dim)
          throw Error(FPCA_EINVAL, "You asked for " + std::to_string(k) + " dimensions, but only " + std::to_string(max_dim) + " allowed");
@@ -595,6 +618,7 @@ int fpca_pca(fpca_ctx *ctx, const fpca_pca_opts *opts, double *U, double *d, dou
       std::string demoted_why;
       {
          HipBackend::Layout lay = HipBackend::plan_layout(ctx, replicated);
+         if (masked && lay != HipBackend::SINGLE) throw Error(FPCA_EINVAL, "fpca_pca: a sample mask is set; sample subsets run on a single context with whole blocks only");
          if (lay == HipBackend::ROWSHARD) {
             const RowShard sh = HipBackend::plan_shard(ctx, lay);
             const long key = ((long)sh.G * 8 + sh.nch) * 128 + b;
@@ -628,8 +652,14 @@ int fpca_pca(fpca_ctx *ctx, const fpca_pca_opts *opts, double *U, double *d, dou
       out.Px = Px;
       out.pve = pve;
       out.partial_rows = opts->partial_rows != 0;
-      std::vector<double> dloc(k);
+      std::vector<double> dloc(k), Uk;
       if (!out.d) out.d = dloc.data();
+      if (masked) { // the solver's U has n_kept rows; Px is put together below
+         if (U || Px) Uk.resize((size_t)Ns * k);
+         out.U = Uk.empty() ? nullptr : Uk.data();
+         out.Px = nullptr;
+         out.partial_rows = false;
+      }
 
       // one solve + the loadings on a given layout; FPCA_ECOMM out of the row-sharded one is caught by the caller below
       auto solve = [&](bool repl) {
@@ -644,11 +674,13 @@ int fpca_pca(fpca_ctx *ctx, const fpca_pca_opts *opts, double *U, double *d, dou
          }
          lap("run_pca");
          const auto tpost = std::chrono::steady_clock::now();
-         if (opts->do_loadings && V) {
+         const bool want_V = opts->do_loadings && V, want_proj = masked && Px;
+         if (want_V || want_proj) {
             // randompca.cpp:191-204: V[:, j] = X' u_j / sqrt(d_j) / sqrt(div); one K2 pass for all k columns
             // (b eigenvectors per Ritz block; ndim > b takes several)
             ctx->ensure(ctx->d_stage, ctx->stage_cap, (size_t)std::max(ctx->N, ctx->P_g) * std::min(k, b));
-            std::vector<double> sc(b);
+            if (want_proj) ensure_io(ctx);
+            std::vector<double> sc(b), isd(b, 1.0 / std::sqrt(div));
             for (int j0 = 0, q = 0; j0 < k; j0 += b, q++) {
                const int nc = std::min(b, k - j0);
                xt_dev(ctx, be.full_ptr(ritz[q]), b, ctx->stream); // (row-sharded solver: gathers the rows of the block from all ranks)
@@ -656,8 +688,18 @@ int fpca_pca(fpca_ctx *ctx, const fpca_pca_opts *opts, double *U, double *d, dou
                for (int j = 0; j < nc; j++) sc[j] = (1.0 / std::sqrt(out.d[j0 + j])) / std::sqrt(div);
                HIP_CHECK(hipMemcpyAsync(ctx->d_small, sc.data(), b * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
                kern::t_to_colmajor(ctx->d_T, ctx->P_g, b, nc, ctx->d_small, ctx->d_stage, ctx->P_g, ctx->stream);
-               staged_download(ctx, ctx->d_stage, ctx->P_g, nc, V + (size_t)j0 * ctx->P_g, (int64_t)ctx->P_g, nullptr, 0, nullptr); // (synchronises:
-                                                                                                  // sc / d_stage are reused by the next block)
+               if (want_V)
+                  staged_download(ctx, ctx->d_stage, ctx->P_g, nc, V + (size_t)j0 * ctx->P_g, (int64_t)ctx->P_g, nullptr, 0, nullptr); // (synchronises:
+                                                                                                     // sc / d_stage are reused by the next block)
+               if (want_proj) {
+                  // X V / sqrt(div) for ALL rows: K3 on the loadings just formed.  On the kept rows this is U sqrt(d) up to rounding (they
+                  // are overwritten with exactly that below), on the others it is what --project computes from these loadings.
+                  kern::colmajor_to_t(ctx->d_stage, ctx->P_g, ctx->P_g, ctx->P_pad, b, nc, ctx->d_T, ctx->stream);
+                  x_dev(ctx, b, ctx->d_io_b, ctx->stream);
+                  kern::block_to_colmajor(ctx->d_io_b, ctx->N, b, nc, ctx->d_stage, ctx->N, ctx->stream);
+                  staged_download(ctx, ctx->d_stage, ctx->N, nc, nullptr, 0, Px + (size_t)j0 * ctx->N, (int64_t)ctx->N, isd.data()); // (synchronises)
+               } else if (!want_V)
+                  HIP_CHECK(hipStreamSynchronize(ctx->stream));
             }
          }
          for (int h : ritz) be.free_block(h);
@@ -708,6 +750,22 @@ int fpca_pca(fpca_ctx *ctx, const fpca_pca_opts *opts, double *U, double *d, dou
       }
       ctx->last_solver_path = path;
       if (info) info->solver_path = path;
+      if (masked && !Uk.empty()) { // kept rows: U and Px = U sqrt(d) as the solver returned them; held-out rows: 0 and the projection
+         const std::vector<uint32_t> &idx = ctx->h_keep_idx;
+         for (int j = 0; j < k; j++) {
+            const double *u = Uk.data() + (size_t)j * Ns;
+            const double sq = std::sqrt(out.d[j]);
+            if (U) {
+               double *o = U + (size_t)j * ctx->N;
+               std::fill(o, o + ctx->N, 0.0);
+               for (uint64_t i = 0; i < Ns; i++) o[idx[i]] = u[i];
+            }
+            if (Px) {
+               double *o = Px + (size_t)j * ctx->N;
+               for (uint64_t i = 0; i < Ns; i++) o[idx[i]] = u[i] * sq;
+            }
+         }
+      }
       if (mean_sd && ctx->P_g) {
          const auto tms = std::chrono::steady_clock::now();
          staged_download(ctx, ctx->d_mean, ctx->P_g, 1, mean_sd, (int64_t)ctx->P_g, nullptr, 0, nullptr);
@@ -731,6 +789,7 @@ int fpca_check(fpca_ctx *ctx, const double *evec, int64_t ldu, const double *eva
 {
    return guarded([&] {
       if (!ctx || !evec || !eval || k < 1 || ldu < (int64_t)ctx->N) throw Error(FPCA_EINVAL, "bad argument to fpca_check");
+      refuse_masked(ctx, "fpca_check");
       const uint64_t N = ctx->N;
       double div = 1; // randompca.cpp:676-680
       if (divisor == FPCA_DIVISOR_N1)

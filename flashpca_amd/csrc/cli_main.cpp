@@ -115,6 +115,9 @@ const OptSpec OPTS[] = {
    {"blockvec", 0, true, "block width of the eigensolver: 16, 32, 48 or 64 [16; 32 / 64 for ndim > 64 / > 128]", true},
    {"maxblocks", 0, true, "basis cap (in blocks) before a thick restart [automatic]", true},
    {"passes", 0, true, "arithmetic of the eigensolver's passes in the exact-integer modes [mixed | exact]: mixed (default) = a solve that needs many passes makes most of them on 4 byte slices of the fp64 operand and puts the Ritz vectors through the exact operator before it declares convergence; exact = every pass on all slices", true},
+   {"keep", 0, true, "PCA on a subset of the samples: only those listed in this file (PLINK's --keep format: FID and IID are the first two fields of each line) enter the statistics and the eigenproblem; eigenvectors, pcs, --outload and --outmeansd are those of the subset, everyone else is projected onto its PCs (--outpcall)", true},
+   {"remove", 0, true, "PCA on a subset of the samples: all but those listed in this file (same format; with --keep: keep first, then remove)", true},
+   {"outpcall", 0, true, "PC output file for ALL samples in .fam order, in the format of the pcs file: the rows of the PCA's samples as in the pcs file, the samples left out by --keep / --remove projected onto the same PCs (written only when asked for)", true},
    {"accum", 0, true, "arithmetic of the two genotype GEMMs [auto | fp64 | fp32 | i8 | i8xS]: i8 = exact-integer int8 MFMA on S = 7 (i8xS: S = 2..8) byte slices of the fp64 operand, results equal to fp64; fp32 = fp32 MFMA products, fp64 long accumulation; auto (default) = i8, or fp64 if the int8 buffers do not fit", true},
 };
 
@@ -654,6 +657,16 @@ int main(int argc, char *argv[])
          std::cerr << "Error: --gpus applies to PCA only (--ucca, --check and --project run on one GPU)" << std::endl;
          return EXIT_FAILURE;
       }
+      const bool subset = has("keep") || has("remove");
+      if (subset && (mode != MODE_PCA || ngpus > 1)) {
+         std::cerr << "Error: --keep / --remove apply to PCA on one GPU only (--check, --project, --ucca and --gpus run on all samples of the fileset)" << std::endl;
+         return EXIT_FAILURE;
+      }
+      if (has("outpcall") && mode != MODE_PCA) {
+         std::cerr << "Error: --outpcall applies to PCA only" << std::endl;
+         return EXIT_FAILURE;
+      }
+      const std::string pcallfile = has("outpcall") ? vm["outpcall"] : "";
       const int blockvec = has("blockvec") ? (int)to_long(vm, "blockvec") : 0;
       const int maxblocks = has("maxblocks") ? (int)to_long(vm, "maxblocks") : 0;
       int accum = FPCA_ACCUM_AUTO;
@@ -741,6 +754,20 @@ int main(int argc, char *argv[])
          parse_bim();
       if (bim_error) std::rethrow_exception(bim_error);
       if (N == 0) throw std::runtime_error("no samples found in " + fam_file);
+      // --keep / --remove: the samples the PCA runs on (everything about the lists is checked here, before any device work)
+      std::vector<uint8_t> keep_mask;
+      std::vector<uint64_t> kept_rows;
+      if (subset) {
+         keep_mask = fpca::read_sample_subset(fam_ids, indiv_ids, has("keep") ? vm["keep"] : "", has("remove") ? vm["remove"] : "");
+         for (uint64_t i = 0; i < N; i++)
+            if (keep_mask[i]) kept_rows.push_back(i);
+         if (kept_rows.size() < 2) {
+            std::cerr << "Error: --keep / --remove leave " << kept_rows.size() << " of " << N << " samples, at least 2 are needed" << std::endl;
+            return EXIT_FAILURE;
+         }
+         verbose && std::cout << timestamp() << "PCA on " << kept_rows.size() << " of " << N << " samples (--keep / --remove)" << std::endl;
+      }
+      const uint64_t N_pca = subset ? kept_rows.size() : N; // samples of the eigenproblem
       phase(".fam / .bim");
       // UCCA: the phenotypes (Data::read_pheno(pheno, 3), data.cpp:408-413), checked against the .fam before any device work.  The
       // reference takes N from this file's rows and then reads the .bed with that N whatever the .fam says; this build refuses.
@@ -791,7 +818,7 @@ int main(int argc, char *argv[])
          const uint64_t P_file = (uint64_t)st.st_size > 3 ? ((uint64_t)st.st_size - 3) / np : 0; // data.cpp:165-170
          P_file_all = P_file;
          // flashpca.cpp:623-633
-         const unsigned max_dim = (unsigned)((std::fmin((double)N, (double)P_file) - 1) / 2.0);
+         const unsigned max_dim = (unsigned)((std::fmin((double)N_pca, (double)P_file) - 1) / 2.0);
          if ((unsigned)n_dim > max_dim) { // (every mode, like the reference)
             std::cerr << "Error: You asked for " << n_dim << " dimensions, but only " << max_dim << "allowed" << std::endl;
             return EXIT_FAILURE;
@@ -990,6 +1017,7 @@ int main(int argc, char *argv[])
             if (Px.empty()) Px.resize((size_t)N * n_dim);
             if (do_loadings && (V.empty() || nsnps != P_file_all)) V.resize((size_t)nsnps * n_dim);
             meansd.resize((size_t)nsnps * 2);
+            if (subset) fpca_ok(fpca_set_sample_mask(ctx, keep_mask.data()));
             rc = fpca_pca(ctx, &o, U.data(), d.data(), Px.data(), pve.data(), do_loadings ? V.data() : nullptr, meansd.data(), &info);
          } else {
             // Eigenvectors / PCs: every rank downloads ITS OWN ROWS (its slice of the row-sharded basis, or an even share of the
@@ -1156,10 +1184,29 @@ int main(int argc, char *argv[])
                colnames_u[i + 1] = "U" + std::to_string(i + 1);
                colnames_pc[i + 1] = "PC" + std::to_string(i + 1);
             }
-            fpca::save_text(ngpus > 1 ? mg.U : U.data(), N, n_dim, colnames_u, rownames, eigvecfile, precision, share); // (--gpus: the shared region)
-
-            std::cout << timestamp() << "Writing " << n_dim << " PCs to file " << pcfile << std::endl;
-            fpca::save_text(ngpus > 1 ? mg.Px : Px.data(), N, n_dim, colnames_pc, rownames, pcfile, precision, share);
+            const double *U_all = ngpus > 1 ? mg.U : U.data(), *Px_all = ngpus > 1 ? mg.Px : Px.data(); // (--gpus: the shared region)
+            if (!subset) {
+               fpca::save_text(U_all, N, n_dim, colnames_u, rownames, eigvecfile, precision, share);
+               std::cout << timestamp() << "Writing " << n_dim << " PCs to file " << pcfile << std::endl;
+               fpca::save_text(Px_all, N, n_dim, colnames_pc, rownames, pcfile, precision, share);
+            } else { // the samples of the PCA only, in .fam order: what a run on the subset fileset writes
+               std::vector<std::string> rn_kept(N_pca);
+               std::vector<double> Mk((size_t)N_pca * n_dim);
+               auto kept_of = [&](const double *M) {
+                  for (int j = 0; j < n_dim; j++)
+                     for (uint64_t i = 0; i < N_pca; i++) Mk[i + (size_t)j * N_pca] = M[kept_rows[i] + (size_t)j * N];
+               };
+               for (uint64_t i = 0; i < N_pca; i++) rn_kept[i] = rownames[kept_rows[i]];
+               kept_of(U_all);
+               fpca::save_text(Mk.data(), N_pca, n_dim, colnames_u, rn_kept, eigvecfile, precision, share);
+               std::cout << timestamp() << "Writing " << n_dim << " PCs to file " << pcfile << std::endl;
+               kept_of(Px_all);
+               fpca::save_text(Mk.data(), N_pca, n_dim, colnames_pc, rn_kept, pcfile, precision, share);
+            }
+            if (!pcallfile.empty()) {
+               std::cout << timestamp() << "Writing " << n_dim << " PCs of all " << N << " samples to file " << pcallfile << std::endl;
+               fpca::save_text(Px_all, N, n_dim, colnames_pc, rownames, pcallfile, precision, share);
+            }
 
             std::cout << timestamp() << "Writing " << n_dim << " proportion variance explained to file " << eigpvefile << std::endl;
             fpca::save_text(pve.data(), n_dim, 1, none, none, eigpvefile, precision);

@@ -136,7 +136,7 @@ void ctx_free(fpca_ctx *c)
    void *ptrs[] = {c->d_Xd, c->d_packed, c->d_lut, c->d_mean, c->d_sd,   c->d_sumsq, c->d_T,
                    c->d_part,   c->d_stage, c->d_io_a, c->d_io_b, c->d_small, c->d_packedT, c->d_packedK2, c->d_inv_sd, c->d_mu_inv_sd,
                    c->d_i8w, c->d_Qb, c->d_Qg, c->d_Qm, c->d_i8ws, c->d_snp_ptr, c->d_snp_idx, c->d_smp_ptr, c->d_smp_idx, c->d_eplane,
-                   c->d_full_in, c->d_full_out, c->d_qrm_loc, c->d_qrm_full, c->d_xmeta, c->d_hyb_idx, c->d_packedE, c->d_packedET, c->d_hyb_T, c->d_hyb_plane, c->d_Qd};
+                   c->d_full_in, c->d_full_out, c->d_qrm_loc, c->d_qrm_full, c->d_xmeta, c->d_hyb_idx, c->d_packedE, c->d_packedET, c->d_hyb_T, c->d_hyb_plane, c->d_Qd, c->d_keep, c->d_keep_bits, c->d_keep_idx};
    for (void *p : ptrs)
       if (p) (void)hipFree(p);
    for (auto &pb : c->block_pool) (void)hipFree(pb.second);
@@ -163,6 +163,10 @@ void ensure_stats(fpca_ctx *c)
 {
    if (c->stats_done) return;
    HIP_CHECK(hipSetDevice(c->device));
+   if (c->masked()) {
+      masked_stats(c);
+      return;
+   }
    uint32_t *d_nmiss = nullptr;
    std::vector<uint32_t> nm(c->P_g);
    if (c->P_g) HIP_CHECK(hipMalloc(&d_nmiss, c->P_g * sizeof(uint32_t)));

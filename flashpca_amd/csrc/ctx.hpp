@@ -12,6 +12,7 @@
 //   ucca.hip            fpca_ucca: per-SNP association with k phenotypes through the K2 pass (+ f_tail.hpp, its F tail)
 //   scca.hip            fpca_scca_prepare / fpca_scca_fit: sparse CCA iterated on the resident P x k matrix C = X'Y (+ scca.hpp)
 //   scca_cv.hip         fpca_scca_cv: K-fold cross-validation of the SCCA penalties, per-fold statistics from one pass over the packed stream
+//   sample_mask.hip     fpca_set_sample_mask: statistics over the kept samples, the row mask of the operator's blocks, kept-row gather / scatter
 // MI355X / gfx950 only; there is no CPU fallback anywhere in the library.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -211,6 +212,15 @@ struct fpca_ctx {
    int prof_used = 0, prof_calls = 0, prof_stride = 1; // every prof_stride-th apply carries the events
    bool prof_on = false;
    fpca_scca_state *scca = nullptr; // released by the next fpca_scca_prepare or by fpca_destroy (scca_free)
+   // sample subset (fpca_set_sample_mask, sample_mask.hip): mean / sd / table / trace are those of the kept samples, the operator's blocks
+   // have zero held-out rows, K3 computes every row.  The packed matrix, its copies and the missing-call lists are those of all N samples.
+   uint64_t n_kept = 0;             // 0: no mask
+   uint8_t *d_keep = nullptr;       // [N_pad] 1 = kept (pad rows 0): the row mask of the blocks
+   uint8_t *d_keep_bits = nullptr;  // [pitch] bit 2 (i % 4) of byte i / 4 set for the kept samples i: the mask row of the statistics kernel
+   uint32_t *d_keep_idx = nullptr;  // [n_kept] the kept samples in input order
+   std::vector<uint32_t> h_keep_idx;
+   bool masked() const { return n_kept != 0; }
+   bool meansd_preloaded = false;   // fpca_set_meansd was called: the standardisation is the caller's, a mask has no say in it
 
    void ensure(double *&p, size_t &cap, size_t need); // grow a device workspace of doubles (context.hip)
    bool multi() const { return comm != nullptr || ar_fn != nullptr || comm_dead; }
@@ -282,6 +292,15 @@ void x_dev(fpca_ctx *c, int b, double *dY, hipStream_t s);        // dY = X_g T
 
 // ---- scca.hip ---------------------------------------------------------------------------------------------
 void scca_free(fpca_ctx *c);
+
+// ---- sample_mask.hip --------------------------------------------------------------------------------------
+void masked_stats(fpca_ctx *c);                                              // ensure_stats under a mask: one pass, kept-sample statistics + all-sample missing counts
+void mask_rows(const fpca_ctx *c, double *blk, int b, hipStream_t s);        // zero the held-out rows of a row-major [N_pad][b] block
+// the kept rows of a block <-> column-major n_kept x ncols (the eigensolver's view of a masked context)
+void gather_kept(const fpca_ctx *c, const double *blk, int b, int ncols, double *out, hipStream_t s);
+void scatter_kept(const fpca_ctx *c, const double *in, int b, int ncols, double *blk, hipStream_t s);
+void refuse_masked(const fpca_ctx *c, const char *fn);                       // FPCA_EINVAL from the entry points that do not run under a mask
+void refuse_shard_while_masked(const fpca_ctx *c, const char *fn);           // ... and from the calls that would make a masked context one shard of several
 
 // ---- download.hip -----------------------------------------------------------------------------------------
 // d_img: device, column-major N x ncols with leading dimension N -> host (ld) and, scaled per column, host2 (ld2); synchronises

@@ -89,6 +89,8 @@ void HipBackend::fill_random(int h, uint64_t seed)
 {
    if (!sharded()) {
       kern::fill_random(blocks_[h], c_->N, c_->N_pad, b_, seed, c_->stream);
+      // a sample mask: the start block lives in the kept rows; every later block is a combination of masked blocks
+      if (c_->masked()) mask_rows(c_, blocks_[h], b_, c_->stream);
       return;
    }
    for (int c = 0; c < sh_.nch; c++) // the rows this rank keeps of the block every rank would have generated
@@ -108,6 +110,7 @@ void HipBackend::apply_begin(int in, int out)
       apply_sharded(c_, sh_, blocks_[in], b_, blocks_[out], c_->stream);
    else
       apply_xxt_dev(c_, blocks_[in], b_, blocks_[out], c_->stream, nullptr);
+   if (c_->masked()) mask_rows(c_, blocks_[out], b_, c_->stream); // K3 computed every row: X_kept X_kept' keeps the kept ones
    HIP_CHECK(hipEventRecord(e1_, c_->stream));
    inflight_ = true;
    inflight_exact_ = !c_->i8_Sc;
@@ -252,6 +255,11 @@ void HipBackend::download2(int h, int ncols, double *host, int64_t ld, double *h
    const double *whole = full_ptr(h); // (row-sharded: a collective -- every rank comes here, whether it wants the result or not)
    if (!host && !host2) return;
    c_->ensure(c_->d_stage, c_->stage_cap, (size_t)c_->N * ncols);
+   if (c_->masked()) {
+      gather_kept(c_, whole, b_, ncols, c_->d_stage, c_->stream);
+      staged_download(c_, c_->d_stage, c_->n_kept, ncols, host, ld, host2, ld2, scale);
+      return;
+   }
    kern::block_to_colmajor(whole, c_->N, b_, ncols, c_->d_stage, c_->N, c_->stream);
    staged_download(c_, c_->d_stage, c_->N, ncols, host, ld, host2, ld2, scale);
 }
@@ -280,6 +288,10 @@ std::vector<std::pair<uint64_t, uint64_t>> HipBackend::rows_of(const fpca_ctx *c
 void HipBackend::download_rows_mine(int h, int ncols, double *host, int64_t ld, double *host2, int64_t ld2, const double *scale)
 {
    if (!host && !host2) return;
+   if (c_->masked()) { // (a single context: all the kept rows are this rank's)
+      download2(h, ncols, host, ld, host2, ld2, scale);
+      return;
+   }
    for (const auto &rg : rows_mine()) {
       const uint64_t g0 = rg.first, n = rg.second - rg.first;
       // where global row g0 sits in this rank's copy of the block
@@ -293,6 +305,13 @@ void HipBackend::download_rows_mine(int h, int ncols, double *host, int64_t ld, 
 void HipBackend::upload(int h, int ncols, const double *host, int64_t ld)
 {
    c_->ensure(c_->d_stage, c_->stage_cap, (size_t)c_->N * ncols);
+   if (c_->masked()) {
+      HIP_CHECK(hipMemcpy2DAsync(c_->d_stage, c_->n_kept * sizeof(double), host, (size_t)ld * sizeof(double), c_->n_kept * sizeof(double), ncols,
+                                 hipMemcpyHostToDevice, c_->stream));
+      scatter_kept(c_, c_->d_stage, b_, ncols, blocks_[h], c_->stream);
+      HIP_CHECK(hipStreamSynchronize(c_->stream));
+      return;
+   }
    HIP_CHECK(hipMemcpy2DAsync(c_->d_stage, c_->N * sizeof(double), host, (size_t)ld * sizeof(double), c_->N * sizeof(double), ncols,
                               hipMemcpyHostToDevice, c_->stream));
    if (!sharded())

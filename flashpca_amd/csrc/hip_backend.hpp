@@ -28,7 +28,8 @@ class HipBackend : public BlockBackend {
    HipBackend(fpca_ctx *c, int b, bool replicated = false, int cheap_S = 0);
    ~HipBackend() override;
 
-   uint64_t nrows() const override { return c_->N; }
+   // (under a sample mask the eigensolver's problem has n_kept rows: download / upload move the kept rows, the blocks keep N_pad)
+   uint64_t nrows() const override { return c_->masked() ? c_->n_kept : c_->N; }
    int width() const override { return b_; }
    int alloc_block() override;
    void free_block(int h) override { used_[h] = 0; }

@@ -18,6 +18,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <thread>
+#include <unordered_map>
 
 #include <sched.h>
 
@@ -117,6 +118,42 @@ TextMatrix read_text(const std::string &filename, unsigned firstcol, long nrows,
       }
    }
    return M;
+}
+
+std::vector<uint8_t> read_sample_subset(const std::vector<std::string> &fam_ids, const std::vector<std::string> &indiv_ids,
+                                        const std::string &keep_file, const std::string &remove_file)
+{
+   const size_t N = fam_ids.size();
+   std::unordered_map<std::string, std::vector<uint32_t>> where; // "FID\tIID" -> its rows of the .fam
+   where.reserve(2 * N);
+   for (size_t i = 0; i < N; i++) where[fam_ids[i] + "\t" + indiv_ids[i]].push_back((uint32_t)i);
+   // flag[i] = 1 for every .fam row named in `filename`
+   auto mark = [&](const std::string &filename, std::vector<uint8_t> &flag) {
+      std::ifstream in(filename, std::ios::in);
+      if (!in) throw std::runtime_error("Error reading file '" + filename + "': " + strerror(errno));
+      std::string line;
+      std::vector<Token> tok;
+      for (uint64_t ln = 1; std::getline(in, line); ln++) {
+         split_ws(line, tok);
+         if (tok.empty()) continue;
+         if (tok.size() < 2)
+            throw std::runtime_error("Error reading file '" + filename + "', line " + std::to_string(ln) + ": expected FID and IID, found one field");
+         const auto it = where.find(tok[0].str() + "\t" + tok[1].str());
+         if (it == where.end())
+            throw std::runtime_error("Error reading file '" + filename + "', line " + std::to_string(ln) + ": sample '" + tok[0].str() + " " + tok[1].str() +
+                                     "' is not in the .fam file");
+         for (uint32_t i : it->second) flag[i] = 1;
+      }
+   };
+   std::vector<uint8_t> keep(N, keep_file.empty() ? 1 : 0);
+   if (!keep_file.empty()) mark(keep_file, keep);
+   if (!remove_file.empty()) {
+      std::vector<uint8_t> rm(N, 0);
+      mark(remove_file, rm);
+      for (size_t i = 0; i < N; i++)
+         if (rm[i]) keep[i] = 0;
+   }
+   return keep;
 }
 
 uint64_t read_fam(const std::string &filename, std::vector<std::string> &fam_ids, std::vector<std::string> &indiv_ids)

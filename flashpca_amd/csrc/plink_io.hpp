@@ -32,6 +32,13 @@ std::vector<double> read_maf(const std::string &filename, const std::vector<std:
 // 504-586) -- and read_plink_fam's two id columns (data.cpp:639-672); same errors as the two calls in that order.
 uint64_t read_fam(const std::string &filename, std::vector<std::string> &fam_ids, std::vector<std::string> &indiv_ids);
 
+// --keep / --remove (PLINK's format): FID and IID are the first two whitespace-separated fields of each line, anything after them is
+// ignored, blank lines are skipped, duplicate lines are harmless.  Returns N bytes, 1 = kept: the samples of keep_file (all when it is
+// empty) minus those of remove_file (none when it is empty).  Throws std::runtime_error for a file that cannot be read, a line with a
+// single field, and an id pair that is not in the .fam.
+std::vector<uint8_t> read_sample_subset(const std::vector<std::string> &fam_ids, const std::vector<std::string> &indiv_ids,
+                                        const std::string &keep_file, const std::string &remove_file);
+
 // (usable_cpus(): common.hpp -- the library sizes its own helper threads with it too)
 
 // save_text (util.h:69-108): header line (if colnames non-empty), then per row  [rowname TAB] v1 TAB v2 ...

@@ -346,6 +346,7 @@ void scca_check_single(const fpca_ctx *c, const char *fn)
    if (c->multi() || (c->rank_known && c->nranks > 1))
       throw Error(FPCA_EINVAL, std::string(fn) + ": the context is one shard of several (a communicator, an all-reduce hook or fpca_set_rank with " +
                                    "more than one rank); SCCA normalises u over all SNPs and runs on a single context only");
+   refuse_masked(c, fn);
 }
 
 void scca_store_c(const double *T, uint64_t P_g, int b, int nc, double scale, double *Cm, int kp, int c0, hipStream_t s)

@@ -205,6 +205,7 @@ extern "C" int fpca_ucca(fpca_ctx *ctx, const double *Y, int64_t ldy, int k, int
 {
    return guarded([&] {
       if (!ctx || !Y || !res) throw Error(FPCA_EINVAL, "bad argument to fpca_ucca (NULL pointer)");
+      refuse_masked(ctx, "fpca_ucca");
       if (k < 1) throw Error(FPCA_EINVAL, "fpca_ucca needs at least one phenotype (k >= 1)");
       if ((uint64_t)k + 2 > ctx->N)
          throw Error(FPCA_EINVAL, "fpca_ucca: " + std::to_string(k) + " phenotypes need at least " + std::to_string((uint64_t)k + 2) +

@@ -160,6 +160,24 @@ int fpca_stats(fpca_ctx *ctx, double *mean_sd, double *trace_out);
 /* preloaded mean/sd (projection path, data.cpp:293-297, randompca.cpp:753-788); P_g x 2 column-major */
 int fpca_set_meansd(fpca_ctx *ctx, const double *mean_sd);
 
+/* Sample subset: PCs fitted on the kept samples, everyone else projected onto them, on the resident packed matrix (no second
+ * .bed of the subset, no --outload / --project round trip).  keep: N bytes, non-zero = kept; NULL clears the mask, after which
+ * the context behaves as a fresh one.  The mask is context state.  While it is set:
+ *   fpca_stats        mean, sd, lookup table and trace are those of the kept samples (K1's formulas in K1's order: bit-identical to
+ *                     K1 on the re-packed subset); a SNP monomorphic among the kept samples is a zero column
+ *   fpca_apply_xt     the held-out rows of B count as zero: T = X_kept' B_kept
+ *   fpca_apply_xxt, fpca_apply_xxt_dev   Y = X_kept X_kept' B on the kept rows, exactly 0 on the others
+ *   fpca_apply_x      all N rows (the projection of the held-out samples under the subset's standardisation)
+ *   fpca_pca          the kept-sample problem: divisor n1 = n_kept - 1, ndim <= (min(n_kept, P) - 1) / 2; U (N x ndim) has zero held-out
+ *                     rows and unit-norm columns; Px is U sqrt(d) on the kept rows and X V / sqrt(div) on the others (V the loadings of
+ *                     the kept-sample problem: what --project computes), from one K2 + K3 pass after the solve; V, mean_sd, pve, trace
+ *                     are those of the kept-sample problem
+ * FPCA_EINVAL, before any device work: a dense context, fewer than 2 kept samples, a context that is one shard of several (and the
+ * calls that would make a masked context one), a preloaded mean/sd (either order), and fpca_check / fpca_ucca / fpca_scca_* /
+ * fpca_scca_cv while a mask is set.  Costs one pass over the packed stream. */
+int fpca_set_sample_mask(fpca_ctx *ctx, const uint8_t *keep);
+uint64_t fpca_nkept(const fpca_ctx *ctx); /* samples the statistics and fpca_pca run on: n_kept under a mask, else N */
+
 /* ------------------------------------------------------------------------------------------------
  * Operator.  b columns at a time; b = 1 is exactly the reference's perform_op.
  *   fpca_apply_xxt : Y = X_g X_g' B        replaces SVDWideOnline::perform_op / perform_op_mat
