@@ -1,4 +1,4 @@
-"""The flashpca drop-in CLI (flashpca_amd/csrc/cli_main.cpp).  CPU part: flag handling and exit codes, which mirror
+"""The flashpca drop-in CLI (flashpca_amd/csrc/cli_options.cpp, cli_multi.cpp, cli_main.cpp).  CPU part: flag handling and exit codes, which mirror
 flashpca.cpp:95-560.  GPU part: end-to-end run on the bundled fileset, outputs compared with the goldens."""
 import json
 import os
