@@ -155,6 +155,7 @@ SIGNATURES = {
     "fpca_debug_k4_bench": (_I, [_P, _I, _I, _I, C.POINTER(_D), C.POINTER(_D)]),
     "fpca_debug_k4_fused": (_I, [_P, _I, _I, _P, _P, _P, _P, _P]),
     "fpca_debug_k4_fused_bench": (_I, [_P, _I, _I, _I, C.POINTER(_D)]),
+    "fpca_debug_k4_inplace": (_I, [_P, _I, _I, _P, _P, _P, _I, _P, _P]),
     "fpca_debug_f_sf": (_I, [_D, _U64, _I, C.POINTER(_D), C.POINTER(_D)]),
     "fpca_debug_fold_stats": (_I, [_P, _P, _I, _P, _I, _P]),
 }

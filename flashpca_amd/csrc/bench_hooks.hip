@@ -183,6 +183,14 @@ int fpca_debug_mfma_i8_probe(const int8_t *A, const int8_t *Bt, int32_t *D)
    });
 }
 
+// The K4 hooks start by filling the context's split-K partial buffer (at the size earlier calls left it) with NaNs (all bits set): a
+// partial plane that a kernel fails to write then shows in the result instead of reading as a zero of fresh memory -- from the
+// second call of a kind on a context on, once the buffer has its size.
+static void poison_partials(fpca_ctx *ctx)
+{
+   if (ctx->be_gpart) HIP_CHECK(hipMemsetAsync(ctx->be_gpart, 0xFF, ctx->be_gpart_cap * sizeof(double), ctx->stream));
+}
+
 int fpca_debug_k4(fpca_ctx *ctx, int b, int nq, const double *V, const double *W, double *C_gram, const double *C_in, int use_init,
                   double *Out, double *G_out)
 {
@@ -190,6 +198,7 @@ int fpca_debug_k4(fpca_ctx *ctx, int b, int nq, const double *V, const double *W
       if (!ctx || !V || !W || nq < 1 || nq > 1000 || (b != 16 && b != 32 && b != 48 && b != 64)) throw Error(FPCA_EINVAL, "bad argument to fpca_debug_k4");
       if ((Out || G_out) && !C_in) throw Error(FPCA_EINVAL, "fpca_debug_k4: Out needs C_in");
       HIP_CHECK(hipSetDevice(ctx->device));
+      poison_partials(ctx);
       HipBackend be(ctx, b);
       const int64_t N = (int64_t)ctx->N;
       std::vector<int> hv(nq);
@@ -202,6 +211,9 @@ int fpca_debug_k4(fpca_ctx *ctx, int b, int nq, const double *V, const double *W
       if (C_gram) be.gram(hv.data(), nq, hw, C_gram);
       if (Out || G_out) {
          const int ho = be.alloc_block();
+         // (a block out of the context's pool may still hold the output of an earlier, identical call: NaNs, so that a row tile the
+         // kernel does not store cannot pass for one it did)
+         if (!be.sharded()) HIP_CHECK(hipMemsetAsync(be.full_ptr(ho), 0xFF, (size_t)ctx->N_pad * b * sizeof(double), ctx->stream));
          if (G_out) // the update and the Gram matrix of its output from one launch (HipBackend::gemm_gram)
             be.gemm_gram(hv.data(), nq, C_in, use_init ? hw : -1, ho, G_out);
          else
@@ -220,6 +232,7 @@ int fpca_debug_k4_fused(fpca_ctx *ctx, int b, int nq, const double *V, const dou
    return guarded([&] {
       if (!ctx || !V || !W || !C_in || !Cg || nq < 1 || nq > 1000 || (b != 16 && b != 32 && b != 48 && b != 64)) throw Error(FPCA_EINVAL, "bad argument to fpca_debug_k4_fused");
       HIP_CHECK(hipSetDevice(ctx->device));
+      poison_partials(ctx);
       HipBackend be(ctx, b);
       const int64_t N = (int64_t)ctx->N;
       std::vector<int> hv(nq);
@@ -232,6 +245,39 @@ int fpca_debug_k4_fused(fpca_ctx *ctx, int b, int nq, const double *V, const dou
       be.gemm_gramvw(hv.data(), nq, C_in, hw, hw, Cg); // (in place, as the solver calls it)
       if (Out) be.download(hw, b, Out, N);
       be.free_block(hw);
+      for (int h : hv) be.free_block(h);
+   });
+}
+
+// HipBackend::gemm / gemm_gram with the output block among the operands, the way solver.cpp calls them:
+//   mode 0: gemm(V, nq, C_in, init = W, out = W);  mode 1: gemm(V, nq, C_in, -1, out = V_{nq-1});  mode 2: gemm_gram of mode 1
+int fpca_debug_k4_inplace(fpca_ctx *ctx, int b, int nq, const double *V, const double *W, const double *C_in, int mode, double *Out, double *G_out)
+{
+   return guarded([&] {
+      if (!ctx || !V || !C_in || !Out || nq < 1 || nq > 1000 || (b != 16 && b != 32 && b != 48 && b != 64) || mode < 0 || mode > 2)
+         throw Error(FPCA_EINVAL, "bad argument to fpca_debug_k4_inplace");
+      if (mode == 0 && !W) throw Error(FPCA_EINVAL, "fpca_debug_k4_inplace: mode 0 needs W");
+      if ((mode == 2) != (G_out != nullptr)) throw Error(FPCA_EINVAL, "fpca_debug_k4_inplace: G_out goes with mode 2");
+      HIP_CHECK(hipSetDevice(ctx->device));
+      poison_partials(ctx);
+      HipBackend be(ctx, b);
+      const int64_t N = (int64_t)ctx->N;
+      std::vector<int> hv(nq);
+      for (int q = 0; q < nq; q++) {
+         hv[q] = be.alloc_block();
+         be.upload(hv[q], b, V + (size_t)q * b * N, N);
+      }
+      int ho = hv[nq - 1];
+      if (mode == 0) {
+         ho = be.alloc_block();
+         be.upload(ho, b, W, N);
+         be.gemm(hv.data(), nq, C_in, ho, ho);
+      } else if (mode == 1)
+         be.gemm(hv.data(), nq, C_in, -1, ho);
+      else
+         be.gemm_gram(hv.data(), nq, C_in, -1, ho, G_out);
+      be.download(ho, b, Out, N); // (the block that was overwritten)
+      if (mode == 0) be.free_block(ho);
       for (int h : hv) be.free_block(h);
    });
 }

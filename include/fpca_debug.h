@@ -57,7 +57,9 @@ int fpca_debug_mfma_peak(int waves_per_simd, int iters, int pattern, double *tfl
  * V: N x (nq b) fp64 column-major with leading dimension N, basis block q = columns [q b, (q+1) b); W: N x b.
  *   C_gram (may be NULL): [q][p][c] = sum_s V_q[s][p] W[s][c]                       nq b b doubles
  *   Out (may be NULL), N x b: (use_init ? W : 0) + sum_q V_q C_in[q]                C_in: [q][p][c], nq b b doubles
- *   G_out (may be NULL): [p][c] = sum_s Out[s][p] Out[s][c], from the SAME launch that writes Out (HipBackend::gemm_gram)  b b doubles */
+ *   G_out (may be NULL): [p][c] = sum_s Out[s][p] Out[s][c], from the SAME launch that writes Out (HipBackend::gemm_gram)  b b doubles
+ * fpca_debug_k4, _k4_fused and _k4_inplace first fill the context's split-K partial buffer, at the size earlier calls left it, with
+ * NaNs: from the second call of a kind on a context on, a partial plane that a kernel does not write shows in the result. */
 int fpca_debug_k4(fpca_ctx *ctx, int b, int nq, const double *V, const double *W, double *C_gram, const double *C_in, int use_init,
                   double *Out, double *G_out);
 /* round 6: the first Gram-Schmidt projection's update and the second projection's Gram matrices from ONE pass over the basis
@@ -65,6 +67,13 @@ int fpca_debug_k4(fpca_ctx *ctx, int b, int nq, const double *V, const double *W
  * q < nq, Cg[nq] = Out' Out -- (nq + 1) b b doubles; and its launch time (kernel + plane reduction) on nq random blocks */
 int fpca_debug_k4_fused(fpca_ctx *ctx, int b, int nq, const double *V, const double *W, const double *C_in, double *Out, double *Cg);
 int fpca_debug_k4_fused_bench(fpca_ctx *ctx, int b, int nq, int reps, double *ms_fused);
+/* HipBackend::gemm / gemm_gram with the output block among the operands, in the forms the solver calls (V, W, C_in as above):
+ *   mode 0: Out = W + sum_q V_q C_in[q], written over W (out = init)
+ *   mode 1: Out = sum_q V_q C_in[q], written over V_{nq-1} (out = the last operand block, no init; W may be NULL)
+ *   mode 2: mode 1 through gemm_gram; G_out: [p][c] = sum_s Out[s][p] Out[s][c], b b doubles (G_out must be NULL in modes 0 and 1)
+ * Out, N x b: the overwritten block, downloaded after the call. */
+int fpca_debug_k4_inplace(fpca_ctx *ctx, int b, int nq, const double *V, const double *W, const double *C_in, int mode, double *Out,
+                          double *G_out);
 /* launch times of the K4 kernels on nq device-resident random basis blocks of this context's height: ms per Gram (kernel + plane
  * reduction) and per block GEMM (Out = Init + sum_q V_q C_q) */
 int fpca_debug_k4_bench(fpca_ctx *ctx, int b, int nq, int reps, double *ms_gram, double *ms_gemm);
