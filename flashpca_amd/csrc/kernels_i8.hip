@@ -1035,15 +1035,29 @@ struct I8Plan {
    unsigned grid;
 };
 
+static bool i8_verbose()
+{
+   static const bool verbose = FPCA_TEST_ENV("FPCA_I8_VERBOSE") != nullptr;
+   return verbose;
+}
+
 static I8Plan i8_plan(uint64_t rows_pad, uint64_t k_pad, const I8Shape &sh, int bw)
 {
    static const char *env_s = FPCA_TEST_ENV("FPCA_I8_SPLITS"); // force plain split-K with this factor
    static int ncu = 0;
    if (!ncu) {
-      hipDeviceProp_t prop;
-      int dev = 0;
-      (void)hipGetDevice(&dev);
-      ncu = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount >= 8) ? prop.multiProcessorCount / 8 * 8 : 256;
+      // FPCA_I8_NCU (test builds): the CU count to plan for, a multiple of 8 -- the two-phase regime at a few thousand rows.  The
+      // grid then exceeds or undercuts the device's CUs, which the kernel does not depend on
+      if (const char *env_n = FPCA_TEST_ENV("FPCA_I8_NCU")) {
+         const int n = atoi(env_n);
+         if (n < 8 || n % 8) throw Error(-1, "FPCA_I8_NCU is a multiple of 8, at least 8");
+         ncu = n;
+      } else {
+         hipDeviceProp_t prop;
+         int dev = 0;
+         (void)hipGetDevice(&dev);
+         ncu = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount >= 8) ? prop.multiProcessorCount / 8 * 8 : 256;
+      }
    }
    const int rtiles = (int)(rows_pad / sh.rows), rtl = (rtiles + 7) / 8, ids = 8 * rtl * sh.zb;
    const int chunks = (int)(k_pad / sh.kc);
@@ -1078,8 +1092,7 @@ static I8Plan i8_plan(uint64_t rows_pad, uint64_t k_pad, const I8Shape &sh, int 
    p.rowB0 = std::min<uint64_t>((uint64_t)qA * 8 * sh.rows, rows_pad);
    p.rowsB = rows_pad - p.rowB0;
    p.grid = (unsigned)(p.nA + (ids - p.nA) * p.sB);
-   static const bool verbose = FPCA_TEST_ENV("FPCA_I8_VERBOSE") != nullptr;
-   if (verbose)
+   if (i8_verbose())
       std::fprintf(stderr, "[fpca] int8 GEMM plan: rows %llu K %llu tile %dx%d zb %d -> %d tile ids, %d chunks; %d unsplit + %d tiles x %d splits (%d chunks each), %u workgroups, est %.3f ms\n",
                    (unsigned long long)rows_pad, (unsigned long long)k_pad, sh.rows, sh.cols, sh.zb, ids, chunks, p.nA, ids - p.nA, p.sB, p.cpsB, p.grid,
                    best * 1e3);
@@ -1133,6 +1146,17 @@ void gemm_i8(const uint8_t *packed, size_t pitch, const int8_t *Qg, const int8_t
    const int bw = i8_bw(b); // Q holds gemm_i8_nsc_pad(S, b) rows; rows >= S*b are zero and carry zero weights
    const I8Plan pl = i8_plan(rows_pad, k_pad, sh, bw);
    const int chunks_total = (int)(k_pad / sh.kc);
+   // (the plan line above is printed for the workspace sizing too: this one marks the plan that is launched, and the instance)
+   if (i8_verbose())
+      std::fprintf(stderr, "[fpca] int8 GEMM launch: %s, mode %d, nt %d%s, %s%s; phase B from row %llu\n", two ? "two operands" : "one operand", mode,
+                   sh.nt, sh.half ? " (half tile)" : "", tiled ? "band-tiled" : "row-major", e_only ? ", E alone" : "", (unsigned long long)pl.rowB0);
+   // FPCA_DEBUG_I8_POISON (test builds): NaNs in exactly the extent of the workspace this plan uses -- plane 0 of every row, planes
+   // 1 .. sB-1 of the phase-B rows -- so that a partial the kernel fails to write cannot pass for the previous launch's value
+   static const bool poison = FPCA_TEST_ENV("FPCA_DEBUG_I8_POISON") != nullptr;
+   if (poison) {
+      const size_t used = ((size_t)rows_pad + (size_t)(pl.sB - 1) * pl.rowsB) * sh.zb * 2 * (size_t)bw;
+      if (hipMemsetAsync(ws, 0xFF, used * sizeof(double), stream) != hipSuccess) throw Error(-3, "gemm_i8: poisoning the workspace failed");
+   }
 #define FPCA_I8_ARGS pl, stream, packed, pitch, Qg, Qm, k_pad, wg, wm, bw, ws, rows_pad, chunks_total, sh.zb, (e_only ? 0x00000100u : 0x00010002u)
    if (gemm_events) (void)hipEventRecord(gemm_events[0], stream);
    if (two && mode == I8_NO_MISSING) throw Error(-1, "gemm_i8: without missing genotypes both matrices share one operand (pass Qm == Qg)");

@@ -109,7 +109,8 @@ def test_shipped_binaries_carry_no_test_switches(built_lib):
     import flashpca_amd as fp
 
     names = [b"FPCA_CLI_TEST", b"FPCA_DEBUG_", b"FPCA_I8_MODE", b"FPCA_I8_SPLITS", b"FPCA_I8_ABL", b"FPCA_GATHER", b"FPCA_AR_CHUNKS",
-             b"FPCA_SPARSE_SIDE_BYTES", b"FPCA_XT_SPLITS", b"FPCA_X_SPLITS", b"FPCA_I8_VERBOSE"]
+             b"FPCA_SPARSE_SIDE_BYTES", b"FPCA_XT_SPLITS", b"FPCA_X_SPLITS", b"FPCA_I8_VERBOSE", b"FPCA_I8_NCU",
+             b"FPCA_DEBUG_I8_POISON"]
     for path in (fp.LIB_PATH, fp.CLI_PATH):
         if os.environ.get("FPCA_LIB"):
             pytest.skip("FPCA_LIB overrides the shipped library")
