@@ -29,9 +29,29 @@ def count_fam_rows(path):
         return f.read().count(b"\n")
 
 
+def _snp_mask(snps, P):
+    """A boolean mask over P SNPs from a boolean mask or an array of unique, in-range indices."""
+    a = np.asarray(snps)
+    if a.dtype == np.bool_:
+        if a.shape != (P,):
+            raise ValueError("a SNP mask must have one entry per SNP (%d), it has shape %s" % (P, a.shape))
+        return a.copy()
+    if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+        raise ValueError("SNPs are selected by a boolean mask or by a one-dimensional array of integer indices")
+    a = a.astype(np.int64)
+    if a.size and (a.min() < 0 or a.max() >= P):
+        raise ValueError("SNP indices must be in 0 .. %d" % (P - 1))
+    if np.unique(a).size != a.size:
+        raise ValueError("SNP indices must be unique")
+    mask = np.zeros(P, dtype=bool)
+    mask[a] = True
+    return mask
+
+
 class Context:
-    def __init__(self, handle):
+    def __init__(self, handle, accum="auto"):
         self.h = handle
+        self._accum_req = accum  # the arithmetic the context was asked for (snp_subset passes it on)
         L = lib()
         self.N = int(L.fpca_nsamples(handle))
         self.P = int(L.fpca_nsnps(handle))
@@ -61,7 +81,7 @@ class Context:
         assert packed.size >= ((N + 3) // 4) * P
         h = C.c_void_p()
         check(lib().fpca_create(C.byref(h), _p(packed), N, P, STANDARDISE[stand], device, ACCUM[accum]))
-        return cls(h)
+        return cls(h, accum)
 
     @classmethod
     def from_bed(cls, bed_path, N, snp_begin=0, P=0, stand="binom2", device=0, accum="fp64"):
@@ -69,7 +89,7 @@ class Context:
         ptot = C.c_uint64(0)
         check(lib().fpca_create_from_bed(C.byref(h), bed_path.encode(), N, snp_begin, P, STANDARDISE[stand], device, ACCUM[accum],
                                          C.byref(ptot)))
-        c = cls(h)
+        c = cls(h, accum)
         c.P_total = int(ptot.value)
         check(lib().fpca_set_total_snps(h, c.P_total))
         return c
@@ -91,7 +111,7 @@ class Context:
         m = _lib.SynthModel(n_pop, fst, missing_rate, int(realistic if maf_model is None else maf_model),
                             int(realistic if missing_model is None else missing_model), conc_frac, lognormal_sigma)
         check(lib().fpca_create_synthetic_model(C.byref(h), N, snp_begin, P, seed, C.byref(m), STANDARDISE[stand], device, ACCUM[accum]))
-        return cls(h)
+        return cls(h, accum)
 
     def close(self):
         if self.h:
@@ -143,6 +163,40 @@ class Context:
     def nkept(self):
         """Samples the statistics and pca() run on (fpca_nkept): the kept ones under a mask, else N."""
         return int(lib().fpca_nkept(self.h))
+
+    # ---- SNP subsets ---------------------------------------------------------------------------------
+    def snp_missing(self):
+        """fpca_snp_missing: K1's per-SNP counts of missing calls over all N samples, a uint32 array."""
+        out = np.empty(self.P, dtype=np.uint32)
+        check(lib().fpca_snp_missing(self.h, _p(out)))
+        return out
+
+    def snp_qc(self, maf=0.0, geno=1.0, keep=None):
+        """fpca_snp_qc: the boolean mask of the SNPs with minor-allele frequency >= maf and missing-call rate <= geno (PLINK's --maf /
+        --geno; maf <= 0 and geno >= 1 switch a filter off), among those of `keep` (a mask or an index array; None: all)."""
+        k8 = np.ascontiguousarray(np.ones(self.P, dtype=bool) if keep is None else _snp_mask(keep, self.P), dtype=np.uint8)
+        n = C.c_uint64(0)
+        check(lib().fpca_snp_qc(self.h, float(maf), float(geno), _p(k8), C.byref(n)))
+        out = k8 != 0
+        assert int(out.sum()) == n.value
+        return out
+
+    def snp_subset(self, keep, accum=None):
+        """fpca_create_snp_subset: a new Context holding the SNPs of `keep` (a boolean mask, or unique in-range indices, which are applied
+        in ascending order), compacted on the device.  accum: the new context's arithmetic (None: what this one was asked for).  This
+        context stays as it is; both matrices are resident until it is closed."""
+        k8 = np.ascontiguousarray(_snp_mask(keep, self.P), dtype=np.uint8)
+        accum = self._accum_req if accum is None else accum
+        h = C.c_void_p()
+        check(lib().fpca_create_snp_subset(C.byref(h), self.h, _p(k8), ACCUM[accum]))
+        return Context(h, accum)
+
+    def snp_subset_bench(self, keep, reps=5):
+        """fpca_debug_snp_subset_bench: (milliseconds per launch, bytes moved per launch) of the record gather alone."""
+        k8 = np.ascontiguousarray(_snp_mask(keep, self.P), dtype=np.uint8)
+        ms, by = C.c_double(0), C.c_double(0)
+        check(lib().fpca_debug_snp_subset_bench(self.h, _p(k8), int(reps), C.byref(ms), C.byref(by)))
+        return ms.value, by.value
 
     def set_total_snps(self, P_total):
         check(lib().fpca_set_total_snps(self.h, int(P_total)))
@@ -398,7 +452,7 @@ class Context:
 
 
 def flashpca(X, ndim=10, stand="binom2", divisor="p", maxiter=500, tol=1e-6, do_loadings=False, return_scale=True,
-             device=0, verbose=False, accum="auto", keep=None, **solver_kw):
+             device=0, verbose=False, accum="auto", keep=None, snps=None, maf=0.0, geno=1.0, **solver_kw):
     """PCA of a PLINK fileset; mirrors flashpca() of the reference's R package for the PLINK-prefix input
     (flashpcaR/R/flashpca.R:99-204 -> flashpca_plink_internal, flashpcaR/src/flashpca.cpp:96-197).
 
@@ -407,10 +461,20 @@ def flashpca(X, ndim=10, stand="binom2", divisor="p", maxiter=500, tol=1e-6, do_
     keep: a boolean array with one entry per sample (PLINK input only): the PCA runs on the kept samples -- values, vectors,
     projection, loadings, center, scale and pve are what a run on the subset fileset returns, rows in input order -- and the result
     gains `projection_all` (N x ndim): the kept samples' rows of `projection`, everyone else projected onto the same PCs.
+    snps: a boolean mask over the .bim rows or an array of unique row indices, e.g. from snp_filter(); maf / geno: PLINK's --maf /
+    --geno on the uploaded matrix (minor-allele frequency >= maf, missing-call rate <= geno; both over all samples, so not together
+    with keep=).  PLINK input only.  The selected SNPs are compacted once on the device and the PCA runs on them: loadings, center and
+    scale have one row per kept SNP, divisor "p" is the kept count, and the result gains `snps_kept`, the mask over the .bim rows.
     Returns values, vectors, projection, loadings, center, scale, pve.
     """
     if divisor not in DIVISOR:
         raise ValueError("divisor must be one of %s" % sorted(DIVISOR))
+    qc = not (maf <= 0 and geno >= 1)  # (a NaN threshold counts as a filter: fpca_snp_qc refuses it)
+    if (snps is not None or qc) and not isinstance(X, str):
+        raise ValueError("snps / maf / geno select SNPs of a PLINK fileset; they do not apply to a numeric matrix")
+    if qc and keep is not None:
+        raise ValueError("maf / geno cannot be combined with keep: PLINK takes these frequencies over the kept samples, the counts here "
+                         "are those of all samples")
     if isinstance(X, str):
         if stand not in STANDARDISE:
             raise ValueError("stand must be one of %s" % sorted(STANDARDISE))  # R: match.arg
@@ -420,6 +484,13 @@ def flashpca(X, ndim=10, stand="binom2", divisor="p", maxiter=500, tol=1e-6, do_
         if stand not in _lib.STANDARDISE_DENSE:
             raise ValueError("stand must be one of %s" % sorted(_lib.STANDARDISE_DENSE))
         ctx = Context.from_dense(np.asarray(X, dtype=np.float64), stand=stand, device=device)
+    snps_kept = None
+    if snps is not None or qc:
+        with ctx as full:
+            snps_kept = np.ones(full.P, dtype=bool) if snps is None else _snp_mask(snps, full.P)
+            if qc:
+                snps_kept = full.snp_qc(maf=maf, geno=geno, keep=snps_kept)
+            ctx = full.snp_subset(snps_kept)  # one compaction of the combined mask; the source is closed on the way out
     with ctx:
         if keep is not None:
             keep = np.asarray(keep)
@@ -432,6 +503,8 @@ def flashpca(X, ndim=10, stand="binom2", divisor="p", maxiter=500, tol=1e-6, do_
     res = dict(values=r["d"], vectors=r["U"], projection=r["Px"], loadings=r["V"], pve=r["pve"], info=r["info"])
     if keep is not None:
         res.update(vectors=r["U"][keep], projection=r["Px"][keep], projection_all=r["Px"])
+    if snps_kept is not None:
+        res["snps_kept"] = snps_kept
     if return_scale:
         res["center"] = r["meansd"][:, 0]
         res["scale"] = r["meansd"][:, 1]
@@ -451,12 +524,14 @@ def _is_012(A):
     return bool(np.all(np.isin(A[~np.isnan(A)], (0.0, 1.0, 2.0))))
 
 
-def ucca(X, Y, standx="binom2", standy="binom2", check_geno=True, check_fam=True, verbose=False, device=0):
+def ucca(X, Y, standx="binom2", standy="binom2", check_geno=True, check_fam=True, verbose=False, device=0, snps=None):
     """Per-SNP canonical correlation (ANOVA of all phenotypes on each SNP, plink.multivariate); mirrors ucca() of the reference's R
     package (flashpcaR/R/ucca.R): same arguments and defaults, its stop() checks raised as ValueError with R's wording.
 
     X: PLINK root name (X.bed / X.bim / X.fam; standx binom or binom2), or a numeric N x P matrix (NaN = missing; any of the five
     standardisations).  Y: N x k phenotypes (NaN = missing, mean-imputed).
+    snps (PLINK input only): a boolean mask over the .bim rows or an array of unique row indices, e.g. from snp_filter(); the scan
+    runs on those SNPs, result and snp_ids have one row per kept SNP, and the mask comes back as snps_kept.
     Returns result (P x 3: R, Fstat, P), npheno and, for the PLINK input, snp_ids in .bim order (ucca_plink_internal,
     flashpcaR/src/flashpca.cpp:275-334).
     """
@@ -464,6 +539,8 @@ def ucca(X, Y, standx="binom2", standy="binom2", check_geno=True, check_fam=True
 
     standx = _match_arg("standx", standx)
     standy = _match_arg("standy", standy)
+    if snps is not None and not isinstance(X, str):
+        raise ValueError("snps selects SNPs of a PLINK fileset; it does not apply to a numeric matrix")
     try:
         Y = np.asarray(Y, dtype=np.float64)
     except (TypeError, ValueError):
@@ -506,6 +583,11 @@ def ucca(X, Y, standx="binom2", standy="binom2", check_geno=True, check_fam=True
         ctx = Context.from_bed(X + ".bed", n, stand=standx, device=device, accum="auto")
     else:
         ctx = Context.from_dense(X, stand=standx, device=device)
+    snps_kept = None
+    if snps is not None:
+        with ctx as full:
+            snps_kept = _snp_mask(snps, full.P)
+            ctx = full.snp_subset(snps_kept)
     with ctx:
         if verbose:
             print("UCCA online mode, N=%d p=%d" % (ctx.N, ctx.P))
@@ -513,6 +595,9 @@ def ucca(X, Y, standx="binom2", standy="binom2", check_geno=True, check_fam=True
     out = dict(result=res, npheno=Y.shape[1])
     if isinstance(X, str):
         out["snp_ids"] = _read_bim(X)[0]
+    if snps_kept is not None:
+        out["snp_ids"] = [s for s, k in zip(out["snp_ids"], snps_kept) if k]
+        out["snps_kept"] = snps_kept
     return out
 
 
@@ -730,6 +815,67 @@ def cv_scca(X, Y, lambda1=np.linspace(1e-6, 1e-3, 5), lambda2=np.linspace(1e-6, 
 def _read_bim(prefix):
     rows = [l.split() for l in open(prefix + ".bim").read().splitlines() if l.strip()]
     return [r[1] for r in rows], [r[4] for r in rows]
+
+
+def _first_fields(src):
+    """SNP ids from an iterable of ids, or from a file in PLINK's --extract / --exclude format (the id is the first field of a line)."""
+    if isinstance(src, (str, bytes)) or hasattr(src, "__fspath__"):
+        with open(src) as f:
+            return {l.split()[0] for l in f if l.strip()}
+    return {str(s) for s in src}
+
+
+def _chrom(c):
+    c = str(c)
+    return c[3:] if c[:3].lower() == "chr" else c
+
+
+def _ranges(src):
+    """(chrom, first_bp, last_bp) triples from an iterable of them, or from a file of lines `chr start end [label]`."""
+    if isinstance(src, (str, bytes)) or hasattr(src, "__fspath__"):
+        with open(src) as f:
+            src = [l.split()[:3] for l in f if l.strip()]
+    out = []
+    for r in src:
+        if len(r) < 3:
+            raise ValueError("a range is (chrom, first_bp, last_bp), found %r" % (r,))
+        out.append((_chrom(r[0]), int(r[1]), int(r[2])))
+    return out
+
+
+def snp_filter(prefix, extract=None, exclude=None, extract_ranges=None, exclude_ranges=None):
+    """A boolean mask over the rows of prefix.bim, for flashpca(snps=), ucca(snps=) and Context.snp_subset().
+
+    extract / exclude: an iterable of SNP ids, or the path of a file in PLINK's format (the id is the first field of each line, blank
+    lines are skipped, duplicates are harmless).  Ids that are not in the .bim are ignored, as PLINK does; an `extract` that matches
+    nothing raises ValueError.  Every .bim row carrying a listed id is selected.
+    extract_ranges / exclude_ranges: (chrom, first_bp, last_bp) triples, or the path of a file of lines `chr start end [label]` (the
+    layout of the reference's exclusion_regions_hg19.txt).  Both ends are inclusive; chromosomes compare as strings after stripping a
+    leading "chr" in either case.
+    Order: extract, then extract_ranges, then exclude, then exclude_ranges."""
+    rows = [l.split() for l in open(prefix + ".bim").read().splitlines() if l.strip()]
+    chrom = np.array([_chrom(r[0]) for r in rows])
+    ids = np.array([r[1] for r in rows])
+    bp = np.array([int(r[3]) for r in rows], dtype=np.int64)
+
+    def in_ranges(src):
+        hit = np.zeros(len(rows), dtype=bool)
+        for c, lo, hi in _ranges(src):
+            hit |= (chrom == c) & (bp >= lo) & (bp <= hi)
+        return hit
+
+    mask = np.ones(len(rows), dtype=bool)
+    if extract is not None:
+        mask &= np.isin(ids, sorted(_first_fields(extract)))
+        if not mask.any():
+            raise ValueError("extract: none of the listed SNP ids is in %s.bim" % prefix)
+    if extract_ranges is not None:
+        mask &= in_ranges(extract_ranges)
+    if exclude is not None:
+        mask &= ~np.isin(ids, sorted(_first_fields(exclude)))
+    if exclude_ranges is not None:
+        mask &= ~in_ranges(exclude_ranges)
+    return mask
 
 
 def project(X, loadings, orig_mean=None, orig_sd=None, ref_alleles=None, divisor="p", device=0, check_bim=True):

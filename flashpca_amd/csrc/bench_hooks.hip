@@ -145,6 +145,49 @@ int fpca_bench_stats(fpca_ctx *ctx, int reps, double *ms_per_launch, double *byt
    });
 }
 
+int fpca_debug_snp_qc_rule(const double *mean, const uint32_t *n_missing, uint64_t N, uint64_t P, double min_maf, double max_missing,
+                           uint8_t *keep, uint64_t *n_kept)
+{
+   return guarded([&] {
+      if (!mean || !n_missing || !keep || N == 0) throw Error(FPCA_EINVAL, "bad argument to fpca_debug_snp_qc_rule");
+      snp_qc_check_thresholds("fpca_debug_snp_qc_rule", min_maf, max_missing);
+      const uint64_t kept = snp_qc_rule(mean, n_missing, N, P, min_maf, max_missing, keep);
+      if (n_kept) *n_kept = kept;
+   });
+}
+
+int fpca_debug_snp_subset_bench(fpca_ctx *src, const uint8_t *keep, int reps, double *ms_per_launch, double *bytes_per_launch)
+{
+   uint8_t *d_dst = nullptr;
+   uint32_t *d_idx = nullptr;
+   hipEvent_t e0 = nullptr, e1 = nullptr;
+   const int rc = guarded([&] {
+      if (!src || !keep || reps < 1 || src->dense) throw Error(FPCA_EINVAL, "bad argument to fpca_debug_snp_subset_bench");
+      const std::vector<uint32_t> idx = kept_indices(keep, src->P_g);
+      if (idx.empty()) throw Error(FPCA_EINVAL, "fpca_debug_snp_subset_bench: the mask keeps no SNP");
+      HIP_CHECK(hipSetDevice(src->device));
+      HIP_ALLOC(hipMalloc(&d_dst, src->pitch * idx.size()));
+      HIP_ALLOC(hipMalloc(&d_idx, idx.size() * sizeof(uint32_t)));
+      HIP_CHECK(hipMemcpy(d_idx, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+      HIP_CHECK(hipEventCreate(&e0));
+      HIP_CHECK(hipEventCreate(&e1));
+      kern::gather_records(src->d_packed, src->pitch, d_idx, idx.size(), d_dst, src->stream);
+      HIP_CHECK(hipEventRecord(e0, src->stream));
+      for (int i = 0; i < reps; i++) kern::gather_records(src->d_packed, src->pitch, d_idx, idx.size(), d_dst, src->stream);
+      HIP_CHECK(hipEventRecord(e1, src->stream));
+      HIP_CHECK(hipEventSynchronize(e1));
+      float ms = 0;
+      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+      if (ms_per_launch) *ms_per_launch = ms / reps;
+      if (bytes_per_launch) *bytes_per_launch = 2.0 * (double)src->pitch * (double)idx.size();
+   });
+   if (e0) (void)hipEventDestroy(e0);
+   if (e1) (void)hipEventDestroy(e1);
+   if (d_dst) (void)hipFree(d_dst);
+   if (d_idx) (void)hipFree(d_idx);
+   return rc;
+}
+
 // diagnostic used by tests/test_gpu_kernels.py: D = A(16x4) B(4x16) through the MFMA operand mapping of kernels.hip
 int fpca_debug_mfma_probe(const double *A, const double *B, double *D)
 {

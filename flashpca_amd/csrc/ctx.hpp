@@ -13,6 +13,8 @@
 //   scca.hip            fpca_scca_prepare / fpca_scca_fit: sparse CCA iterated on the resident P x k matrix C = X'Y (+ scca.hpp)
 //   scca_cv.hip         fpca_scca_cv: K-fold cross-validation of the SCCA penalties, per-fold statistics from one pass over the packed stream
 //   sample_mask.hip     fpca_set_sample_mask: statistics over the kept samples, the row mask of the operator's blocks, kept-row gather / scatter
+//   snp_subset.hip      fpca_snp_missing / fpca_snp_qc / fpca_create_snp_subset: the QC rule on K1's counts, the record gather that compacts
+//                       the kept SNPs into a new context
 // MI355X / gfx950 only; there is no CPU fallback anywhere in the library.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -301,6 +303,13 @@ void gather_kept(const fpca_ctx *c, const double *blk, int b, int ncols, double 
 void scatter_kept(const fpca_ctx *c, const double *in, int b, int ncols, double *blk, hipStream_t s);
 void refuse_masked(const fpca_ctx *c, const char *fn);                       // FPCA_EINVAL from the entry points that do not run under a mask
 void refuse_shard_while_masked(const fpca_ctx *c, const char *fn);           // ... and from the calls that would make a masked context one shard of several
+
+// ---- snp_subset.hip ---------------------------------------------------------------------------------------
+// host only: keep[j] != 0 stays 1 unless maf = min(mean / 2, 1 - mean / 2) < min_maf (min_maf > 0) or n_missing / N > max_missing
+// (max_missing < 1); a SNP without a call counts as maf 0; entries that are 0 stay 0.  Returns the number left non-zero.
+uint64_t snp_qc_rule(const double *mean, const uint32_t *n_missing, uint64_t N, uint64_t P, double min_maf, double max_missing, uint8_t *keep);
+std::vector<uint32_t> kept_indices(const uint8_t *keep, uint64_t P); // ascending record numbers of keep[j] != 0 (FPCA_EINVAL for P >= 2^32)
+void snp_qc_check_thresholds(const char *fn, double min_maf, double max_missing); // FPCA_EINVAL: NaN, min_maf > 0.5, max_missing < 0
 
 // ---- download.hip -----------------------------------------------------------------------------------------
 // d_img: device, column-major N x ncols with leading dimension N -> host (ld) and, scaled per column, host2 (ld2); synchronises

@@ -13,6 +13,9 @@ namespace kern {
 // back-to-back records of np bytes -> rows of `pitch` bytes (upload path)
 void repitch(const uint8_t *src, uint64_t np, uint64_t nrec, uint8_t *dst, size_t pitch, hipStream_t stream);
 void fix_last_byte(uint8_t *packed, size_t pitch, uint64_t np, int valid_in_last, uint64_t P_g, hipStream_t stream);
+// record gather (snp_subset.hip): dst[j][:] = src[idx[j]][:] over `pitch` bytes (a multiple of 16) for j < nrec; dst has the same pitch,
+// nothing at or after record nrec is written
+void gather_records(const uint8_t *src, size_t pitch, const uint32_t *idx, uint64_t nrec, uint8_t *dst, hipStream_t stream);
 
 // K1: per-SNP code counts -> mean, sd, lookup table (by raw PLINK code), sum of squares
 //   lut [P_pad][4], mean/sd/sumsq [P_pad]; rows >= P_g untouched (must be pre-zeroed)

@@ -178,6 +178,31 @@ int fpca_set_meansd(fpca_ctx *ctx, const double *mean_sd);
 int fpca_set_sample_mask(fpca_ctx *ctx, const uint8_t *keep);
 uint64_t fpca_nkept(const fpca_ctx *ctx); /* samples the statistics and fpca_pca run on: n_kept under a mask, else N */
 
+/* SNP subset: the analyses run on a list of SNPs, or on those that pass a minor-allele-frequency / call-rate filter, without a second
+ * fileset.  The kept records are compacted ONCE, on the device, into a new context; that context is an ordinary one, so PCA, the
+ * operator, UCCA, SCCA and cv.scca run on it unchanged.
+ *   fpca_snp_missing        n_missing[P_g]: K1's per-SNP counts of missing calls over all N samples (K1 runs if nobody has).
+ *   fpca_snp_qc             keep[P_g] is input and output: an entry that is 0 stays 0 (list filters and QC filters compose), a non-zero
+ *                           entry becomes 1 or 0; *n_kept (may be NULL) = entries left non-zero.  From K1's per-SNP mean and missing
+ *                           count, on the host: p = mean / 2, maf = min(p, 1 - p), dropped when maf < min_maf; miss = n_missing / N,
+ *                           dropped when miss > max_missing.  Both comparisons strict, as in PLINK (--maf, --geno): a SNP exactly at a
+ *                           threshold stays.  min_maf <= 0 / max_missing >= 1 disable a filter; a SNP without a single call counts as
+ *                           maf = 0.  FPCA_EINVAL for a NaN threshold, min_maf > 0.5, max_missing < 0.
+ *                           Both calls: FPCA_EINVAL for a dense context, while a sample mask is set (the counts are all-sample counts)
+ *                           and after fpca_set_meansd (K1 never counted).
+ *   fpca_create_snp_subset  a NEW, fresh context on src's device with src's N and standardisation method, whose SNPs are the records of
+ *                           src with keep[j] != 0 (keep: P_g bytes), in order; accum: any FPCA_ACCUM_*, as for fpca_create.  Nothing else
+ *                           of src is inherited (statistics, sample mask, preloaded mean/sd, SCCA state); its own SNP count is its total
+ *                           (fpca_set_total_snps).  src is left untouched and usable.  The new packed matrix is byte for byte what
+ *                           fpca_create builds from the re-packed kept records.  One record gather at HBM speed (pitch * P_kept bytes
+ *                           read, as many written); the call returns after one synchronise.  Source and subset are resident together
+ *                           until the caller destroys the source: FPCA_ENOMEM, with both sizes in the message, when the second matrix
+ *                           does not fit.  FPCA_EINVAL, before any device work: out, src or keep NULL, a dense src, a src that is one
+ *                           shard of several (a communicator, an all-reduce hook, fpca_set_rank with more than one rank), zero kept SNPs. */
+int fpca_snp_missing(fpca_ctx *ctx, uint32_t *n_missing);
+int fpca_snp_qc(fpca_ctx *ctx, double min_maf, double max_missing, uint8_t *keep, uint64_t *n_kept);
+int fpca_create_snp_subset(fpca_ctx **out, fpca_ctx *src, const uint8_t *keep, int accum);
+
 /* ------------------------------------------------------------------------------------------------
  * Operator.  b columns at a time; b = 1 is exactly the reference's perform_op.
  *   fpca_apply_xxt : Y = X_g X_g' B        replaces SVDWideOnline::perform_op / perform_op_mat

@@ -87,6 +87,14 @@ int fpca_debug_f_sf(double r2, uint64_t n, int k, double *F, double *P);
  * are the fold's size minus the three); mean_sd (may be NULL): P_g x 2 like fpca_stats, the mean / sd over the samples OUTSIDE fold
  * which_fold as fpca_scca_cv installs them for that fold.  The context is not changed. */
 int fpca_debug_fold_stats(fpca_ctx *ctx, const uint8_t *fold, int nfolds, uint32_t *counts, int which_fold, double *mean_sd);
+/* diagnostic (tests): the QC rule of fpca_snp_qc on caller arrays, no context and no device involved: mean[P] and n_missing[P] as K1
+ * leaves them, N samples; keep[P] in and out, as for fpca_snp_qc.  FPCA_EINVAL for the thresholds fpca_snp_qc refuses. */
+int fpca_debug_snp_qc_rule(const double *mean, const uint32_t *n_missing, uint64_t N, uint64_t P, double min_maf, double max_missing,
+                           uint8_t *keep, uint64_t *n_kept);
+/* time the record gather of fpca_create_snp_subset alone (scripts/snp_subset_measure.py): the destination and the index list are
+ * allocated before the clock starts; one untimed launch, then `reps` timed ones on src's stream.  Milliseconds per launch and the bytes
+ * one launch moves (2 pitch P_kept: read and written).  src is not changed. */
+int fpca_debug_snp_subset_bench(fpca_ctx *src, const uint8_t *keep, int reps, double *ms_per_launch, double *bytes_per_launch);
 
 #ifdef __cplusplus
 }
