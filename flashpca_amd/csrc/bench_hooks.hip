@@ -440,6 +440,34 @@ int fpca_debug_k4_bench(fpca_ctx *ctx, int b, int nq, int reps, double *ms_gram,
    });
 }
 
+// The split-K plans of the fp64 / fp32 / dense kernels, from the helpers the launches themselves use (operator.hip fp_k2_splits /
+// fp_k3_splits, kernels.hip *_chunks): nothing is launched.
+int fpca_debug_fp_plan(fpca_ctx *ctx, int b, int out[6])
+{
+   return guarded([&] {
+      if (!ctx || !out || b < 1 || b > MAX_BLOCKVEC) throw Error(FPCA_EINVAL, "bad argument to fpca_debug_fp_plan");
+      const int bw = pad16(b);
+      const bool fp32 = ctx->accum == FPCA_ACCUM_FP32;
+      const int s2 = fp_k2_splits(ctx, bw), s3 = fp_k3_splits(ctx, bw);
+      const kern::SplitChunks c2 = ctx->dense ? kern::xt_b_dense_chunks(ctx->N_pad, s2) : kern::xt_b_chunks(ctx->N_pad, bw, s2);
+      const kern::SplitChunks c3 = ctx->dense ? kern::x_t_dense_chunks(ctx->P_pad, s3) : kern::x_t_chunks(ctx->P_pad, bw, s3, fp32);
+      out[0] = s2, out[1] = c2.per_split, out[2] = c2.total;
+      out[3] = s3, out[4] = c3.per_split, out[5] = c3.total;
+   });
+}
+
+// NaNs (all bits set) into the operator's split-K partial buffer and into T, at the sizes earlier calls left them: a partial plane or
+// a tile of T that the next product fails to write then shows in its result instead of reading as the previous call's value.
+int fpca_debug_poison_partials(fpca_ctx *ctx)
+{
+   return guarded([&] {
+      if (!ctx) throw Error(FPCA_EINVAL, "bad argument to fpca_debug_poison_partials");
+      HIP_CHECK(hipSetDevice(ctx->device));
+      if (ctx->d_part) HIP_CHECK(hipMemsetAsync(ctx->d_part, 0xFF, ctx->part_cap * sizeof(double), ctx->stream));
+      if (ctx->d_T) HIP_CHECK(hipMemsetAsync(ctx->d_T, 0xFF, ctx->T_cap * sizeof(double), ctx->stream));
+   });
+}
+
 int fpca_debug_mfma_peak(int waves_per_simd, int iters, int pattern, double *tflops)
 {
    return guarded([&] {

@@ -291,6 +291,9 @@ void apply_xxt_dev(fpca_ctx *c, const double *dB, int b, double *dY, hipStream_t
 void apply_sharded(fpca_ctx *c, const RowShard &sh, const double *in_slice, int b, double *out_slice, hipStream_t s);
 void xt_dev(fpca_ctx *c, const double *dB, int b, hipStream_t s); // T (in the context) = X_g' dB
 void x_dev(fpca_ctx *c, int b, double *dY, hipStream_t s);        // dY = X_g T
+// split-K factors of the fp64 / fp32 / dense kernels for this context and block width, as the three functions above launch them
+int fp_k2_splits(const fpca_ctx *c, int b);
+int fp_k3_splits(const fpca_ctx *c, int b);
 
 // ---- scca.hip ---------------------------------------------------------------------------------------------
 void scca_free(fpca_ctx *c);

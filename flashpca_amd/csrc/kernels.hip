@@ -550,15 +550,25 @@ static int pick_splits(uint64_t tiles, uint64_t chunks, int min_chunks, int max_
    return best;
 }
 
+static constexpr int xt_b_kc(int b) { return b <= 32 ? 128 : 64; } // XtCfg<NT>::KC
+
 int xt_b_splits(uint64_t N_pad, uint64_t P_pad, int b, bool fp32)
 {
-   const int kc = b <= 32 ? 128 : 64; // XtCfg<NT>::KC
+   const int kc = xt_b_kc(b);
    const int tile = ((fp32 && b >= 48) || (!fp32 && b == 16)) ? 128 : 256; // 64 XtMt<RT, NT>::MT
    static const int forced = FPCA_ENV_INT("FPCA_XT_SPLITS", 0);
    if (forced > 0) return (int)std::min<uint64_t>(forced, N_pad / kc);
    // fp64 with b <= 32 needs 145 VGPRs and 40 KB of LDS: three workgroups per CU are resident
    const uint64_t slots = (!fp32 && b <= 32) ? 768 : 512;
    return pick_splits(P_pad / tile, N_pad / kc, 4, 64, slots);
+}
+
+SplitChunks xt_b_chunks(uint64_t N_pad, int b, int nsplit)
+{
+   const int kc = xt_b_kc(b), chunks_total = (int)(N_pad / kc);
+   int cps = (chunks_total + nsplit - 1) / nsplit;
+   if (kc == 128) cps += cps & 1; // super-chunks of two (k_xt_b): every split starts on an even chunk (N_pad is a multiple of 512)
+   return {chunks_total, cps};
 }
 
 template <typename RT, int NT> struct XtMt {
@@ -574,9 +584,8 @@ static void launch_xt_b(const uint8_t *packed, size_t pitch, const double *lut, 
                         uint64_t N_pad, uint64_t P_pad, int nsplit, hipStream_t stream)
 {
    constexpr int KC = XtCfg<NT>::KC;
-   const int chunks_total = (int)(N_pad / KC);
-   int cps = (chunks_total + nsplit - 1) / nsplit;
-   if (KC == 128) cps += cps & 1; // super-chunks of two (k_xt_b): every split starts on an even chunk (N_pad is a multiple of 512)
+   static_assert(KC == xt_b_kc(16 * NT), "xt_b_chunks and the kernel's chunk");
+   const SplitChunks sc = xt_b_chunks(N_pad, 16 * NT, nsplit);
    constexpr int MT = XtMt<RT, NT>::MT;
    const size_t smem = ((size_t)KC * 16 * NT + 64 * MT * (NT == 1 ? 32 : 4)) * sizeof(RT); // B tile + table (16 columns: [SNP][16] pairs)
    static bool attr_set = false;
@@ -586,7 +595,7 @@ static void launch_xt_b(const uint8_t *packed, size_t pitch, const double *lut, 
    }
    dim3 grid((unsigned)(P_pad / (64 * MT)), (unsigned)nsplit);
    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_xt_b<RT, NT, MT, KC>), grid, dim3(256), smem, stream, packed, pitch, lut, B, Tpart, P_pad,
-                      chunks_total, cps);
+                      sc.total, sc.per_split);
    HIP_CHECK_LAUNCH();
 }
 
@@ -779,7 +788,7 @@ template <typename RT, int NT> struct XCfg {
    static constexpr int KCX = (MIXED && NT >= 3) ? 32 : 64;
 };
 static inline int x_t_mt(int b, bool fp32) { return fp32 ? 4 : (b <= 32 ? 8 : 4); }
-static inline int x_t_kc(int b, bool fp32) { return (fp32 && b >= 48) ? 32 : 64; }
+static constexpr int x_t_kc(int b, bool fp32) { return (fp32 && b >= 48) ? 32 : 64; }
 
 int x_t_splits(uint64_t N_pad, uint64_t P_pad, int b, bool fp32)
 {
@@ -788,13 +797,19 @@ int x_t_splits(uint64_t N_pad, uint64_t P_pad, int b, bool fp32)
    return pick_splits(N_pad / (64 * x_t_mt(b, fp32)), P_pad / x_t_kc(b, fp32), 4, 64, 512);
 }
 
+SplitChunks x_t_chunks(uint64_t P_pad, int b, int nsplit, bool fp32)
+{
+   const int chunks_total = (int)(P_pad / x_t_kc(b, fp32));
+   return {chunks_total, (chunks_total + nsplit - 1) / nsplit};
+}
+
 template <typename RT, int NT>
 static void launch_x_t(const uint8_t *packed, size_t pitch, const double *lut, const double *T, double *Ypart,
                        uint64_t N_pad, uint64_t P_pad, int nsplit, hipStream_t stream)
 {
    constexpr int MT = XCfg<RT, NT>::MT, KCX = XCfg<RT, NT>::KCX;
-   const int chunks_total = (int)(P_pad / KCX);
-   const int cps = (chunks_total + nsplit - 1) / nsplit;
+   static_assert(KCX == x_t_kc(16 * NT, XCfg<RT, NT>::MIXED), "x_t_chunks and the kernel's chunk");
+   const SplitChunks sc = x_t_chunks(P_pad, 16 * NT, nsplit, XCfg<RT, NT>::MIXED);
    const size_t smem = (size_t)KCX * 16 * MT + ((size_t)KCX * 16 * NT + KCX * 32) * sizeof(RT); // packed tile, T tile, [KCX][16] table pairs
    static bool attr_set = false;
    if (!attr_set) {
@@ -804,7 +819,7 @@ static void launch_x_t(const uint8_t *packed, size_t pitch, const double *lut, c
    }
    dim3 grid((unsigned)(N_pad / (64 * MT)), (unsigned)nsplit);
    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_x_t<RT, MT, NT, KCX>), grid, dim3(256), smem, stream, packed, pitch, lut, T, Ypart,
-                      N_pad, chunks_total, cps);
+                      N_pad, sc.total, sc.per_split);
    HIP_CHECK_LAUNCH();
 }
 
@@ -1142,14 +1157,33 @@ __global__ __launch_bounds__(256, 2) void k_x_t_dense(const double *__restrict__
          for (int r = 0; r < 4; r++) Yout[(s_wave + 4 * (kq + 4 * r) + m) * b + nt * 16 + li] = acc[m][nt][r];
 }
 
-int xt_b_dense_splits(uint64_t N_pad, uint64_t P_pad) { return pick_splits(P_pad / 128, N_pad / 64, 8, 64, 768); }
-int x_t_dense_splits(uint64_t N_pad, uint64_t P_pad) { return pick_splits(N_pad / 256, P_pad / 64, 8, 64, 768); }
+// (FPCA_XT_SPLITS / FPCA_X_SPLITS, test builds: force the plan, as for the packed kernels)
+int xt_b_dense_splits(uint64_t N_pad, uint64_t P_pad)
+{
+   static const int forced = FPCA_ENV_INT("FPCA_XT_SPLITS", 0);
+   if (forced > 0) return (int)std::min<uint64_t>(forced, N_pad / 64);
+   return pick_splits(P_pad / 128, N_pad / 64, 8, 64, 768);
+}
+int x_t_dense_splits(uint64_t N_pad, uint64_t P_pad)
+{
+   static const int forced = FPCA_ENV_INT("FPCA_X_SPLITS", 0);
+   if (forced > 0) return (int)std::min<uint64_t>(forced, P_pad / 64);
+   return pick_splits(N_pad / 256, P_pad / 64, 8, 64, 768);
+}
+// 64 samples (K2d) / 64 SNPs (K3d) per chunk: the kernels' KC
+static SplitChunks dense_chunks(uint64_t len, int nsplit)
+{
+   const int chunks_total = (int)(len / 64);
+   return {chunks_total, (chunks_total + nsplit - 1) / nsplit};
+}
+SplitChunks xt_b_dense_chunks(uint64_t N_pad, int nsplit) { return dense_chunks(N_pad, nsplit); }
+SplitChunks x_t_dense_chunks(uint64_t P_pad, int nsplit) { return dense_chunks(P_pad, nsplit); }
 
 void xt_b_dense(const double *Xd, const double *B, double *Tpart, uint64_t N_pad, uint64_t P_pad, int b, int nsplit,
                 hipStream_t stream)
 {
-   const int chunks_total = (int)(N_pad / 64);
-   const int cps = (chunks_total + nsplit - 1) / nsplit;
+   const SplitChunks sc = xt_b_dense_chunks(N_pad, nsplit);
+   const int chunks_total = sc.total, cps = sc.per_split;
    dim3 grid((unsigned)(P_pad / 128), (unsigned)nsplit);
    const size_t smem = (size_t)64 * b * 8;
    switch (b) {
@@ -1165,8 +1199,8 @@ void xt_b_dense(const double *Xd, const double *B, double *Tpart, uint64_t N_pad
 void x_t_dense(const double *Xd, const double *T, double *Ypart, uint64_t N_pad, uint64_t P_pad, int b, int nsplit,
                hipStream_t stream)
 {
-   const int chunks_total = (int)(P_pad / 64);
-   const int cps = (chunks_total + nsplit - 1) / nsplit;
+   const SplitChunks sc = x_t_dense_chunks(P_pad, nsplit);
+   const int chunks_total = sc.total, cps = sc.per_split;
    dim3 grid((unsigned)(N_pad / 256), (unsigned)nsplit);
    const size_t smem = (size_t)64 * b * 8;
    switch (b) {

@@ -38,6 +38,14 @@ void reduce_sum(const double *part, double *out, uint64_t count, int nsplit, hip
 // heuristics (host): number of splits for K2 / K3 given the problem and the chip (256 CUs, 2 WGs/CU)
 int xt_b_splits(uint64_t N_pad, uint64_t P_pad, int b, bool fp32);
 int x_t_splits(uint64_t N_pad, uint64_t P_pad, int b, bool fp32);
+// what a launch with `nsplit` splits hands its kernel: chunks of the reduction in all, and chunks per split (workgroup row y owns
+// chunks [y cps, min((y + 1) cps, total)) -- a short or empty range stores a short sum or a plane of zeros).  The launchers take
+// their numbers from these, and so does fpca_debug_fp_plan.
+struct SplitChunks {
+   int total, per_split;
+};
+SplitChunks xt_b_chunks(uint64_t N_pad, int b, int nsplit);
+SplitChunks x_t_chunks(uint64_t P_pad, int b, int nsplit, bool fp32);
 
 // Dense (in-memory fp64 matrix) path: Xd [P_pad][N_pad] fp64, one row per column of the caller's N x P matrix
 // util.cpp:24-192 in place (method 0 none, 1 sd, 2 binom, 3 binom2, 4 center; NaN = missing); mean/sd/sumsq [P_pad]
@@ -45,6 +53,8 @@ void dense_standardise(double *Xd, uint64_t N_pad, uint64_t N, uint64_t P_g, int
                        double *sumsq, hipStream_t stream);
 int xt_b_dense_splits(uint64_t N_pad, uint64_t P_pad);
 int x_t_dense_splits(uint64_t N_pad, uint64_t P_pad);
+SplitChunks xt_b_dense_chunks(uint64_t N_pad, int nsplit);
+SplitChunks x_t_dense_chunks(uint64_t P_pad, int nsplit);
 void xt_b_dense(const double *Xd, const double *B, double *Tpart, uint64_t N_pad, uint64_t P_pad, int b, int nsplit,
                 hipStream_t stream);
 void x_t_dense(const double *Xd, const double *T, double *Ypart, uint64_t N_pad, uint64_t P_pad, int b, int nsplit,

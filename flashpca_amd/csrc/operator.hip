@@ -10,6 +10,15 @@ using namespace fpca;
 
 namespace fpca {
 
+int fp_k2_splits(const fpca_ctx *c, int b)
+{
+   return c->dense ? kern::xt_b_dense_splits(c->N_pad, c->P_pad) : kern::xt_b_splits(c->N_pad, c->P_pad, b, c->accum == FPCA_ACCUM_FP32);
+}
+int fp_k3_splits(const fpca_ctx *c, int b)
+{
+   return c->dense ? kern::x_t_dense_splits(c->N_pad, c->P_pad) : kern::x_t_splits(c->N_pad, c->P_pad, b, c->accum == FPCA_ACCUM_FP32);
+}
+
 // the operator on device-resident blocks: dY = X_g X_g' dB (+ all-reduce).  ev (optional): 4 events recorded
 // at [start, after K2(+reduce), after K3(+reduce), after all-reduce].
 void apply_xxt_dev(fpca_ctx *c, const double *dB, int b, double *dY, hipStream_t s, hipEvent_t *ev, bool reduce)
@@ -59,8 +68,8 @@ void apply_xxt_dev(fpca_ctx *c, const double *dB, int b, double *dY, hipStream_t
       if (ev) HIP_CHECK(hipEventRecord(ev[3], s));
       return;
    }
-   const int s2 = c->dense ? kern::xt_b_dense_splits(c->N_pad, c->P_pad) : kern::xt_b_splits(c->N_pad, c->P_pad, b, c->accum == FPCA_ACCUM_FP32);
-   const int s3 = c->dense ? kern::x_t_dense_splits(c->N_pad, c->P_pad) : kern::x_t_splits(c->N_pad, c->P_pad, b, c->accum == FPCA_ACCUM_FP32);
+   const int s2 = fp_k2_splits(c, b);
+   const int s3 = fp_k3_splits(c, b);
    c->ensure(c->d_T, c->T_cap, (size_t)c->P_pad * b);
    size_t need = 0;
    if (s2 > 1) need = std::max(need, (size_t)s2 * c->P_pad * b);
@@ -203,7 +212,7 @@ void xt_dev(fpca_ctx *c, const double *dB, int b, hipStream_t s)
       xt_i8(c, dB, b, s, false);
       return;
    }
-   const int s2 = c->dense ? kern::xt_b_dense_splits(c->N_pad, c->P_pad) : kern::xt_b_splits(c->N_pad, c->P_pad, b, c->accum == FPCA_ACCUM_FP32);
+   const int s2 = fp_k2_splits(c, b);
    c->ensure(c->d_T, c->T_cap, (size_t)c->P_pad * b);
    if (s2 > 1) c->ensure(c->d_part, c->part_cap, (size_t)s2 * c->P_pad * b);
    if (c->dense)
@@ -221,7 +230,7 @@ void x_dev(fpca_ctx *c, int b, double *dY, hipStream_t s)
       x_i8(c, b, dY, s, false);
       return;
    }
-   const int s3 = c->dense ? kern::x_t_dense_splits(c->N_pad, c->P_pad) : kern::x_t_splits(c->N_pad, c->P_pad, b, c->accum == FPCA_ACCUM_FP32);
+   const int s3 = fp_k3_splits(c, b);
    if (s3 > 1) c->ensure(c->d_part, c->part_cap, (size_t)s3 * c->N_pad * b);
    if (c->dense)
       kern::x_t_dense(c->d_Xd, c->d_T, s3 > 1 ? c->d_part : dY, c->N_pad, c->P_pad, b, s3, s);

@@ -78,6 +78,16 @@ int fpca_debug_k4_inplace(fpca_ctx *ctx, int b, int nq, const double *V, const d
  * reduction) and per block GEMM (Out = Init + sum_q V_q C_q) */
 int fpca_debug_k4_bench(fpca_ctx *ctx, int b, int nq, int reps, double *ms_gram, double *ms_gemm);
 
+/* diagnostic (tests/test_gpu_fp_splits.py): the split-K plans fpca_apply_xt / fpca_apply_x / fpca_apply_xxt launch on this context's
+ * fp64, fp32 or dense kernels for a block of b columns (1 .. 64, rounded up to 16 as the operator does), from the very host
+ * functions the launches take their numbers from; nothing runs on the device.
+ *   out[0..2]: X'B -- splits, chunks per split as handed to the kernel, chunks in all;   out[3..5]: the same for X T.
+ * Split i owns chunks [i out[1], min((i + 1) out[1], out[2])): the last one may be short, and trailing ones empty. */
+int fpca_debug_fp_plan(fpca_ctx *ctx, int b, int out[6]);
+/* fills the operator's split-K partial buffer and its T buffer, at the capacity earlier calls left them, with NaNs on the context's
+ * stream: after one product has sized them, a plane or tile that the next product does not write shows in its result */
+int fpca_debug_poison_partials(fpca_ctx *ctx);
+
 /* diagnostic (tests): the F tail of fpca_ucca, from the host build of the same source the finishing kernel runs (no device
  * involved): F = r2 / (1 - r2) (n - k - 1) / k and P = upper tail of F(k, n - k - 1) at F = I_{1 - r2}((n - k - 1) / 2, k / 2).
  * FPCA_EINVAL unless k >= 1 and n >= k + 2. */
