@@ -34,6 +34,7 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 typedef double d2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u2 __attribute__((ext_vector_type(2)));
 
 #define HIP_CHECK_LAUNCH()                                                                         \
    do {                                                                                             \
@@ -474,7 +475,8 @@ void i8_dequant_rows(const int8_t *Qrm, uint64_t rows, int b, int S, const Slice
 //   K = SNPs).  TWO = false (K2): both integer matrices multiply the same operand Q.  TWO = true (K3): G.M multiplies
 //   Qg (slices of T/sd), M multiplies Qm (slices of mean T/sd).
 //   Workgroup = 4 waves, ONE wave per SIMD with the whole 512-register budget (up to 256 accumulator AGPRs), arranged
-//   WR x WC; a wave owns MT x NT tiles of 32x32 of both matrices (2 MT NT <= 16 accumulators).  Operand tiles
+//   WR x WC; a wave owns MT x NT tiles of 32x32 of both matrices (2 MT NT <= 16 accumulators).  (Or 8 x 1 waves, two per SIMD with
+//   256 registers each, around the same operand tiles -- the G.M-alone kernel at 512 rows, see I8Cfg and i8_tile_rows.)  Operand tiles
 //   [WC NT 32 columns][KC k] are double-buffered in LDS (row stride KC + 16 B: the 16 lanes of a ds_read_b128 group hit
 //   distinct banks); the packed words go straight from global memory to the registers of the lane that decodes them.
 //   Decode: a lane's dword w holds 16 codes; (w >> 2q) & 0x03030303 leaves codes q, q+4, q+8, q+12 in the four bytes
@@ -501,11 +503,22 @@ __device__ __forceinline__ u4 gload16(const void *sbase, uint32_t voff) // expli
    asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(r) : "v"(voff), "s"(sbase), "n"(OFF));
    return r;
 }
+__device__ __forceinline__ u2 gload8(const void *sbase, uint32_t voff) // ... 8 bytes, address = sbase + voff
+{
+   u2 r;
+   asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(r) : "v"(voff), "s"(sbase));
+   return r;
+}
 // hand-placed waits; the "+v" operands make the consumers of the loaded registers depend on the wait
 __device__ __forceinline__ void lds_wait(v4i &a) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a)); }
 __device__ __forceinline__ void lds_wait(v4i &a, v4i &b) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b)); }
 template <int N>
 __device__ __forceinline__ void vm_wait(u4 &a)
+{
+   asm volatile("s_waitcnt vmcnt(%1)" : "+v"(a) : "n"(N));
+}
+template <int N>
+__device__ __forceinline__ void vm_wait(u2 &a)
 {
    asm volatile("s_waitcnt vmcnt(%1)" : "+v"(a) : "n"(N));
 }
@@ -551,7 +564,10 @@ struct I8Cfg {
    static constexpr int MATS = MODE == I8_NO_MISSING ? 1 : 2;
    static constexpr int NTF = HALF ? NT - 1 : NT;       // full 32-column tiles
    static_assert(!(TWO && MATS == 1), "without E there is only one operand");
-   static_assert(WR * WC == 4 && MATS * MT * NT <= 16 && (MT == 1 || G == 1) && G <= NT, "shape");
+   // 8 waves (WR = 8): two waves per SIMD under ONE set of operand tiles -- 512 rows, the register budget of two co-resident
+   // 4-wave workgroups, half their operand staging (the largest L2 -> L1 stream of the 4-wave kernel)
+   static_assert((WR * WC == 4 || (WR == 8 && WC == 1)) && MATS * MT * NT <= 16 && (MT == 1 || G == 1) && G <= NT, "shape");
+   static constexpr int WAVES = WR * WC, THREADS = 64 * WAVES;
    static_assert(!HALF || (WC == 1 && MT == 2 && G == 1 && MODE != I8_SKIP_EMPTY && (KC / 32) % 2 == 0), "half-tile variant");
    static constexpr int ROWS = WR * MT * 32;            // workgroup rows
    static constexpr int COLS = WC * NT * 32 - (HALF ? 16 : 0); // workgroup columns of each operand
@@ -562,21 +578,26 @@ struct I8Cfg {
    static constexpr int LDQH = LDQ + (HALF ? 16 : 0);   // row stride of the remainder tile's rows
    static constexpr int QTILE = COLS * LDQ + (HALF ? 16 * 16 : 0); // bytes of one operand tile
    static constexpr int STAGE = NQ * QTILE;
-   static constexpr int SEGS = KC / 16, RSTEP = 256 / SEGS; // 16-byte segments per row; rows covered by 256 threads
-   static constexpr int NP1 = COLS / RSTEP;             // pieces per thread per operand tile
+   static constexpr int SEGS = KC / 16, RSTEP = THREADS / SEGS; // 16-byte segments per row; rows covered by one piece of every thread
+   // HALF with 512 threads: the 16 rows of the remainder tile are half a piece -- every thread takes 8 bytes of them instead
+   // (512 x 8 B = 16 rows of KC = 256), so that all waves issue the same loads and count the same waits
+   static constexpr bool HALF8 = HALF && RSTEP == 32;
+   static constexpr int NP1 = HALF8 ? (COLS - 16) / RSTEP + 1 : COLS / RSTEP; // pieces per thread per operand tile
    static constexpr int NP = NQ * NP1;                  // ... per chunk
    static constexpr int KS = KC / 32;                   // 32-k steps per chunk
    static constexpr int PW = KC / 128;                  // 16-byte packed pieces per lane per m-tile (lane half = KC/2 k)
    static constexpr int NSTEP = KS * MT * G;            // micro-steps per chunk
    static constexpr int H = NSTEP / 2;
-   // dynamic LDS: the double-buffered operand tiles; the epilogue reuses it for 4 waves x NT dumped tiles + the weights
-   static constexpr int LDS_NEED = (2 * STAGE > 4 * NT * 4096 + 2 * WC * NT * 32 * 8) ? 2 * STAGE : 4 * NT * 4096 + 2 * WC * NT * 32 * 8;
+   // dynamic LDS: the double-buffered operand tiles; the epilogue reuses it for WAVES x NT dumped tiles + the weights
+   static constexpr int LDS_EPI = WAVES * NT * 4096 + 2 * WC * NT * 32 * 8;
+   static constexpr int LDS_NEED = (2 * STAGE > LDS_EPI) ? 2 * STAGE : LDS_EPI;
    // The narrowest column block (2 tiles: 136 registers, 34 KB) would fit three workgroups per CU; measured at 500,000 x
    // 100,000 (scripts/r4_narrow_probe.sh, GEMM kernels K2 / K3): three per CU 4.61 / 4.74 ms, two 4.31 / 4.39, one 5.20 / 5.74 --
    // so it asks for enough LDS to be two (the wider blocks are two or one by their registers: 224+ of 512).
-   static constexpr int LDS_BYTES = (!TWO && NT <= 2 && LDS_NEED < 56 * 1024) ? 56 * 1024 : LDS_NEED;
-   static_assert(COLS % RSTEP == 0 && NSTEP % 2 == 0 && LDS_BYTES <= 160 * 1024, "staging");
-   static_assert(!HALF || RSTEP == 16, "the remainder tile is the last staging piece");
+   // (an 8-wave workgroup is alone on its CU by its waves: nothing to ask for)
+   static constexpr int LDS_BYTES = (!TWO && NT <= 2 && WAVES == 4 && LDS_NEED < 56 * 1024) ? 56 * 1024 : LDS_NEED;
+   static_assert((HALF8 ? (COLS - 16) % RSTEP == 0 && KC == 256 : COLS % RSTEP == 0) && NSTEP % 2 == 0 && LDS_BYTES <= 160 * 1024, "staging");
+   static_assert(!HALF || RSTEP == 16 || HALF8, "the remainder tile is the last staging piece");
 };
 
 // returns (MODE == I8_SKIP_EMPTY) whether any lane of the wave holds a missing genotype in this 32-row x 32-k block
@@ -602,7 +623,7 @@ __device__ __forceinline__ bool i8_decode(uint32_t w, v4i &ag, v4i &am, uint32_t
 }
 
 template <class C>
-__global__ __launch_bounds__(256, 1) void k_gemm_i8(const uint8_t *__restrict__ packed, size_t pitch,
+__global__ __launch_bounds__(C::THREADS, 1) void k_gemm_i8(const uint8_t *__restrict__ packed, size_t pitch,
                                                      const int8_t *__restrict__ Qg, const int8_t *__restrict__ Qm,
                                                      uint64_t k_pad, const double *__restrict__ wg, const double *__restrict__ wm, int bw,
                                                      double *__restrict__ part, uint64_t rows_pad, int chunks_total, int zb,
@@ -628,7 +649,8 @@ __global__ __launch_bounds__(256, 1) void k_gemm_i8(const uint8_t *__restrict__ 
    // UNSPLIT (phase A: no partial planes beyond plane 0, the whole round streams the operand in lock-step); the
    // remaining nB < #CU.. tiles, which would otherwise be a mostly idle last round, are cut sB ways along K (phase B,
    // workgroup ids nA + split * nB + k).  nA = 0 is plain split-K.
-   const int rtiles = (int)(rows_pad / C::ROWS), rtl = (rtiles + 7) / 8, ids = 8 * rtl * zb, nB = ids - nA;
+   // (8 waves: rows_pad is a multiple of 256, so the last 512-row tile may be half a tile -- see `idle`)
+   const int rtiles = (int)((rows_pad + (C::WAVES == 8 ? C::ROWS - 1 : 0)) / C::ROWS), rtl = (rtiles + 7) / 8, ids = 8 * rtl * zb, nB = ids - nA;
    int w0 = blockIdx.x, split = 0, c_begin = 0, c_end = chunks_total;
    if (w0 >= nA) {
       const int wp = w0 - nA;
@@ -642,6 +664,9 @@ __global__ __launch_bounds__(256, 1) void k_gemm_i8(const uint8_t *__restrict__ 
    if (rt >= rtiles || c_begin >= c_end) return;
    const uint64_t row0 = (uint64_t)rt * C::ROWS;
    const int col0 = zblk * C::COLS;
+   // 8 waves, last half tile: the waves whose rows lie behind rows_pad stage their share of the operand tiles and reach every barrier,
+   // but load no packed words and write no partials (wave-uniform; never true with 4 waves)
+   const bool idle = C::WAVES == 8 && __builtin_amdgcn_readfirstlane((int)(row0 + (uint64_t)(wr * 32 * MT) >= rows_pad)) != 0;
 
    v16i acc[MATS][MT][NT]; // [mat][m][n]   (HALF: the last n is never touched and costs nothing)
    v4i acch[MATS][MT][2];  // HALF: the 16-column remainder, rows 16 t .. 16 t + 15 of m-tile m in acch[mat][m][t]
@@ -673,13 +698,20 @@ __global__ __launch_bounds__(256, 1) void k_gemm_i8(const uint8_t *__restrict__ 
    // HALF: lane (column j = lane & 15, quarter qd = lane >> 4) of the 16x16x64 operand reads k-half qd >> 1 of k-step 2 kp + (qd & 1)
    const uint32_t aQh0 = lds_base + (uint32_t)(32 * NTF * LDQ + (lane & 15) * C::LDQH) + ((lane >> 5) & 1) * (KC / 2) + ((lane >> 4) & 1) * 16;
 
+   // (8 waves with the half tile: the remainder tile's 16 rows are one 8-byte piece per thread, row tid / 32, bytes 8 (tid % 32) ..)
+   const uint32_t qvoffh = (uint32_t)((tid / 32) * k_pad + (tid % 32) * 8);
+   const int qdsth = (tid / 32) * C::LDQH + (tid % 32) * 8;
    u4 qreg[NP];
+   u2 qregh[NQ];
    u4 pk[MT][PW], pkn[MT][PW]; // packed words of the current / next chunk (one dword per k-step)
 
    auto issue_q = [&](auto rr, int cc) {
       constexpr int r = decltype(rr)::value, o = r / NP1, r1 = r % NP1;
       const int8_t *sb = ((TWO && o) ? Qm : Qg) + (uint64_t)(col0 + C::RSTEP * r1) * k_pad + (uint64_t)cc * KC;
-      qreg[r] = gload16<0>(sb, qvoff);
+      if constexpr (C::HALF8 && r1 == NP1 - 1)
+         qregh[o] = gload8(sb, qvoffh);
+      else
+         qreg[r] = gload16<0>(sb, qvoff);
    };
    auto issue_p = [&](u4(&dst)[MT][PW], int cc) {
       const uint8_t *pb = prow + (size_t)cc * (C::TILED ? 2048 : KC / 4);
@@ -689,25 +721,46 @@ __global__ __launch_bounds__(256, 1) void k_gemm_i8(const uint8_t *__restrict__ 
          if constexpr (PW == 2) dst[m][1] = gload16<(C::TILED ? 1024 : 16)>(pb, pvoff[m]);
       }
    };
-   auto store_q = [&](auto rr, unsigned char *st) {
-      constexpr int r = decltype(rr)::value, o = r / NP1, r1 = r % NP1;
-      vm_wait<NP - 1 - r + NPK>(qreg[r]); // loads are issued in the order q[0..NP), p[..]
-      // (HALF: the last piece is the remainder tile's 16 rows, at their own pitch)
-      const int hoff = (HALF && r1 == NP1 - 1) ? (tid / C::SEGS) * (C::LDQH - LDQ) : 0;
-      *reinterpret_cast<u4 *>(st + o * C::QTILE + r1 * C::RSTEP * LDQ + hoff) = qreg[r];
+   auto store_q = [&](auto rr, unsigned char *st, auto behind) { // `behind`: loads issued after the NP pieces (the packed words, or none)
+      constexpr int r = decltype(rr)::value, o = r / NP1, r1 = r % NP1, NB = decltype(behind)::value;
+      if constexpr (C::HALF8 && r1 == NP1 - 1) {
+         vm_wait<NP - 1 - r + NB>(qregh[o]);
+         *reinterpret_cast<u2 *>(st - qdst + qdsth + o * C::QTILE + r1 * C::RSTEP * LDQ) = qregh[o];
+      } else {
+         vm_wait<NP - 1 - r + NB>(qreg[r]); // loads are issued in the order q[0..NP), p[..]
+         // (HALF: the last piece is the remainder tile's 16 rows, at their own pitch)
+         const int hoff = (HALF && r1 == NP1 - 1) ? (tid / C::SEGS) * (C::LDQH - LDQ) : 0;
+         *reinterpret_cast<u4 *>(st + o * C::QTILE + r1 * C::RSTEP * LDQ + hoff) = qreg[r];
+      }
    };
 
-   // prologue: chunk c_begin
-   static_for<NP>([&](auto rr) { issue_q(rr, c_begin); });
-   issue_p(pk, c_begin);
-   static_for<NP>([&](auto rr) { store_q(rr, smem + qdst); });
+   constexpr std::integral_constant<int, NPK> after_p{};
+   constexpr std::integral_constant<int, 0> after_none{};
+   if (idle) {
+      // the staging alone, chunk by chunk, barrier for barrier what the working waves do below
+      static_for<NP>([&](auto rr) { issue_q(rr, c_begin); });
+      static_for<NP>([&](auto rr) { store_q(rr, smem + qdst, after_none); });
+      __syncthreads();
+      for (int c = c_begin; c < c_end; c++) {
+         const int cn = (c + 1 < c_end) ? c + 1 : c;
+         unsigned char *wst = smem + (size_t)(((c - c_begin) & 1) ^ 1) * C::STAGE + qdst;
+         static_for<NP>([&](auto rr) { issue_q(rr, cn); });
+         static_for<NP>([&](auto rr) { store_q(rr, wst, after_none); });
+         __syncthreads();
+      }
+   } else {
+      // prologue: chunk c_begin
+      static_for<NP>([&](auto rr) { issue_q(rr, c_begin); });
+      issue_p(pk, c_begin);
+      static_for<NP>([&](auto rr) { store_q(rr, smem + qdst, after_p); });
 #pragma unroll
-   for (int m = 0; m < MT; m++)
+      for (int m = 0; m < MT; m++)
 #pragma unroll
-      for (int h = 0; h < PW; h++) vm_wait<0>(pk[m][h]);
-   __syncthreads();
+         for (int h = 0; h < PW; h++) vm_wait<0>(pk[m][h]);
+      __syncthreads();
+   }
 
-   for (int c = c_begin; c < c_end; c++) {
+   for (int c = idle ? c_end : c_begin; c < c_end; c++) {
       const int buf = (c - c_begin) & 1;
       const int cn = (c + 1 < c_end) ? c + 1 : c; // the last chunk re-stages itself (branch-free pipeline)
       const uint32_t aQ = aQ0 + (uint32_t)buf * C::STAGE, aQ2 = aQ + C::QTILE;
@@ -774,7 +827,7 @@ __global__ __launch_bounds__(256, 1) void k_gemm_i8(const uint8_t *__restrict__ 
          if constexpr (s == H - 1) issue_p(pkn, cn);
          if constexpr (s >= H) {
             static_for<(s - H + 1) * NP / H - (s - H) * NP / H>([&](auto jj) {
-               store_q(std::integral_constant<int, (s - H) * NP / H + decltype(jj)::value>{}, wst);
+               store_q(std::integral_constant<int, (s - H) * NP / H + decltype(jj)::value>{}, wst, after_p);
             });
          }
          // --- operand fragments of the next micro-step
@@ -859,14 +912,15 @@ __global__ __launch_bounds__(256, 1) void k_gemm_i8(const uint8_t *__restrict__ 
    // tiles are dead by now; 4 KB per tile and wave) and the recombination runs from LDS with a handful of registers.
    __syncthreads(); // every wave has finished reading the operand tiles
    constexpr int WREG = NT * 4096; // bytes of a wave's private tile area: [NT][32 rows][32 cols] int32
-   double *sW = reinterpret_cast<double *>(smem + 4 * WREG); // weights of this workgroup's slice-columns: [2][COLS]
+   double *sW = reinterpret_cast<double *>(smem + C::WAVES * WREG); // weights of this workgroup's slice-columns: [2][COLS]
    constexpr int WCOLS = C::WC * NT * 32; // (HALF: the 16 columns missing from the last tile carry zero weights)
-   for (int t = tid; t < WCOLS; t += 256) {
+   for (int t = tid; t < WCOLS; t += C::THREADS) {
       sW[t] = t < C::COLS ? wg[col0 + t] : 0.0;
       sW[WCOLS + t] = t < C::COLS ? wm[col0 + t] : 0.0;
    }
    __syncthreads();
-   static_assert(C::LDS_BYTES >= 4 * WREG + 2 * WCOLS * 8, "epilogue LDS layout");
+   static_assert(C::LDS_BYTES >= C::WAVES * WREG + 2 * WCOLS * 8, "epilogue LDS layout");
+   if (idle) return; // (behind the last barrier)
    int *sT = reinterpret_cast<int *>(smem + wave * WREG);
    const double *sWl = sW + wc * 32 * NT + li;
    const int kb = bw / 32; // a lane's tiles n, n + kb, ... feed the same virtual column 32 ((tile0 + n) % kb) + li
@@ -981,17 +1035,62 @@ __global__ __launch_bounds__(256) void k_i8_combine(const double *__restrict__ p
 
 // ---- shape selection ----
 // The slice-columns (S*b, rounded up to whole 32-column tiles) are cut into `zb` equal column blocks of NT tiles
-// (blockIdx.z); 4 x 1 waves per workgroup either way, KC = 256:
+// (blockIdx.z); 4 x 1 waves per workgroup, KC = 256:
 //   K2: wave = 32 rows x NT <= 8 tiles (every packed row is decoded exactly once; any S without padding for b = 32)
 //   K3: wave = 64 rows x NT = 3..4 tiles of BOTH operands (two operand tiles per stage -> half the columns per block)
+// ... or 8 x 1 waves of 64 rows (512-row tiles) for the G.M-alone kernel at 3.5 and at 2 tiles, where two 4-wave workgroups share a
+// CU anyway and each stages its own copy of the operand tile: i8_tile_rows decides per launch.
 // Measured alternatives at cfg3, S = 8 (K2 / K3 ms): 2 x 2 waves of 64 x 128 | 128 x 64: 19.2 / 22.4; K3 with 32-row waves,
 // all tiles and KC = 128: 24.3; K2 with the K3 shape: 18.9 -- versus 18.7 / 20.6 for the shapes kept.
 struct I8Shape {
    int nt, zb, rows, cols, kc;
    bool half; // the last tile is the 16-column remainder (v_mfma_i32_16x16x64_i8), cols = 32 nt - 16
+   bool wide; // an 8-wave instance (512 rows) of this shape exists
 };
 
-static I8Shape i8_shape(int S, int b, bool two, int mode = I8_FULL)
+static int i8_ncu()
+{
+   static int ncu = 0;
+   if (!ncu) {
+      // FPCA_I8_NCU (test builds): the CU count to plan for, a multiple of 8 -- the two-phase regime at a few thousand rows.  The
+      // grid then exceeds or undercuts the device's CUs, which the kernel does not depend on
+      if (const char *env_n = FPCA_TEST_ENV("FPCA_I8_NCU")) {
+         const int n = atoi(env_n);
+         if (n < 8 || n % 8) throw Error(-1, "FPCA_I8_NCU is a multiple of 8, at least 8");
+         ncu = n;
+      } else {
+         hipDeviceProp_t prop;
+         int dev = 0;
+         (void)hipGetDevice(&dev);
+         ncu = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount >= 8) ? prop.multiProcessorCount / 8 * 8 : 256;
+      }
+   }
+   return ncu;
+}
+
+// Tile height of one launch: 512 rows (8 waves under one operand tile) where the instance exists, rows_pad is whole 256-row units (the
+// last 512-row tile may then be half a tile; the row ranges of the chunked all-reduce need not be) and the launch has at least
+// I8_WIDE_QUARTERS / 4 rounds of 512-row tiles.  Measured at cfg3 on 256 CUs (profiles/wide_ab.txt): K3, 977 tiles, 5.41 -> 5.28 ms;
+// K2, 196 tiles (3/4 of a round, plain split-K), 5.30 -> 5.25 ms -- and the apply with both 0.11 ms below the apply with K3 alone,
+// every run of six: three quarters of a round it is.  The 2-tile instance (4-slice passes) is slower than its 4-wave twin (K3 3.76 ->
+// 3.91 ms) and never chosen.  FPCA_I8_ROWS=256|512 (test
+// builds) forces the choice wherever an instance exists.
+constexpr int I8_WIDE_QUARTERS = 3;
+static int i8_tile_rows(uint64_t rows_pad, int ncu, const I8Shape &sh)
+{
+   if (!sh.wide || !rows_pad || rows_pad % 256) return sh.rows;
+   static const char *env_r = FPCA_TEST_ENV("FPCA_I8_ROWS");
+   if (env_r) {
+      const int r = atoi(env_r);
+      if (r != 256 && r != 512) throw Error(-1, "FPCA_I8_ROWS is 256 or 512");
+      return r == 512 ? 512 : sh.rows;
+   }
+   const uint64_t tiles512 = (rows_pad + 511) / 512;
+   return (sh.half && sh.nt == 4 && tiles512 * 4 >= (uint64_t)I8_WIDE_QUARTERS * ncu) ? 512 : sh.rows;
+}
+
+// rows_pad: the rows of the launch the shape is for (0: the 4-wave shape, whatever the launch)
+static I8Shape i8_shape(int S, int b, bool two, int mode = I8_FULL, uint64_t rows_pad = 0)
 {
    const int tiles = (S * b + 31) / 32, cap = two ? 4 : 8; // largest instantiated block
    // smallest instantiated block: 2 tiles (few slices of a narrow block: S = 4, b = 16 is 64 slice-columns).  Rounds 2-5 had the
@@ -1011,8 +1110,10 @@ static I8Shape i8_shape(int S, int b, bool two, int mode = I8_FULL)
    sh.half = mode != I8_SKIP_EMPTY && sh.zb == 1 && S * b == 32 * sh.nt - 16 && (sh.nt == 4 || (sh.nt == 2 && !two && mode == I8_NO_MISSING));
    if (sh.half) {
       sh.cols -= 16;
-      sh.rows = 256; // (every half-tile instantiation is 4 waves x 64 rows, the two-matrix K2 one included)
+      sh.rows = 256; // (every half-tile instantiation is 4 or 8 waves x 64 rows, the two-matrix K2 one included)
    }
+   sh.wide = !two && mode == I8_NO_MISSING && sh.zb == 1 && ((sh.nt == 4 && sh.half) || (sh.nt == 2 && !sh.half));
+   if (rows_pad) sh.rows = i8_tile_rows(rows_pad, i8_ncu(), sh);
    return sh;
 }
 
@@ -1022,7 +1123,8 @@ int gemm_i8_nsc_pad(int S, int b)
    return std::max(s2.zb * 32 * s2.nt, s3.zb * 32 * s3.nt); // (whole tiles: the zero rows behind S*b carry zero weights)
 }
 
-// Work decomposition of one GEMM launch (see k_gemm_i8): one workgroup per CU, so whole rounds of #CU tiles run unsplit
+// Work decomposition of one GEMM launch (see k_gemm_i8): one workgroup per CU (the 512-row tiles; two of the 256-row one-matrix
+// tiles are co-resident, which the plan ignores -- its times are relative), so whole rounds of #CU tiles run unsplit
 // (phase A) and only the leftover tiles are split along K (phase B); each extra split of phase B costs a partial plane
 // for ITS rows only.  Plain split-K (nA = 0) is kept for problems with less than one round of tiles.
 // (A stream-K schedule -- one persistent workgroup per CU walking a contiguous range of (tile, chunk) units -- was built
@@ -1044,24 +1146,10 @@ static bool i8_verbose()
 static I8Plan i8_plan(uint64_t rows_pad, uint64_t k_pad, const I8Shape &sh, int bw)
 {
    static const char *env_s = FPCA_TEST_ENV("FPCA_I8_SPLITS"); // force plain split-K with this factor
-   static int ncu = 0;
-   if (!ncu) {
-      // FPCA_I8_NCU (test builds): the CU count to plan for, a multiple of 8 -- the two-phase regime at a few thousand rows.  The
-      // grid then exceeds or undercuts the device's CUs, which the kernel does not depend on
-      if (const char *env_n = FPCA_TEST_ENV("FPCA_I8_NCU")) {
-         const int n = atoi(env_n);
-         if (n < 8 || n % 8) throw Error(-1, "FPCA_I8_NCU is a multiple of 8, at least 8");
-         ncu = n;
-      } else {
-         hipDeviceProp_t prop;
-         int dev = 0;
-         (void)hipGetDevice(&dev);
-         ncu = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount >= 8) ? prop.multiProcessorCount / 8 * 8 : 256;
-      }
-   }
-   const int rtiles = (int)(rows_pad / sh.rows), rtl = (rtiles + 7) / 8, ids = 8 * rtl * sh.zb;
+   const int ncu = i8_ncu();
+   const int rtiles = (int)((rows_pad + (sh.rows == 512 ? 511 : 0)) / sh.rows), rtl = (rtiles + 7) / 8, ids = 8 * rtl * sh.zb;
    const int chunks = (int)(k_pad / sh.kc);
-   const double t_chunk = 2.2e-6 * (double)sh.rows * sh.cols * sh.kc / (128.0 * 256 * 256); // one workgroup-chunk at ~3 POP/s
+   const double t_chunk = 2.2e-6 * (double)sh.rows * sh.cols * sh.kc / (128.0 * 256 * 256); // one workgroup-chunk at ~3 POP/s per CU: in proportion to the tile's rows
    const double t_seg = 5e-6;                                                               // prologue + epilogue of a workgroup
    const double t_row_plane = 2.0 * bw * 8 * 2 * sh.rows / 3.0e12;                          // one tile's partial, written + read
    double best = 1e30;
@@ -1109,7 +1197,7 @@ size_t gemm_i8_workspace_doubles(uint64_t rows_pad, uint64_t k_pad, int S, int b
    size_t need = 0;
    for (int mode : {(int)I8_FULL, (int)I8_SKIP_EMPTY, (int)I8_NO_MISSING}) { // (the shapes differ: only FULL / NO_MISSING have the half tile)
       if (two && mode == I8_NO_MISSING) continue;
-      const I8Shape sh = i8_shape(S, b, two, mode);
+      const I8Shape sh = i8_shape(S, b, two, mode, rows_pad); // (the tile height gemm_i8 will choose for these rows)
       const I8Plan p = i8_plan(rows_pad, k_pad, sh, i8_bw(b));
       need = std::max(need, ((size_t)rows_pad + (size_t)(p.sB - 1) * p.rowsB) * sh.zb * 2 * (size_t)i8_bw(b));
    }
@@ -1125,7 +1213,7 @@ static void launch_i8(const I8Plan &pl, hipStream_t stream, const uint8_t *packe
       (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gemm_i8<C>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
       attr_set = true;
    }
-   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gemm_i8<C>), dim3(pl.grid), dim3(256), C::LDS_BYTES, stream, packed, pitch, Qg, Qm, k_pad, wg, wm, bw,
+   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gemm_i8<C>), dim3(pl.grid), dim3(C::THREADS), C::LDS_BYTES, stream, packed, pitch, Qg, Qm, k_pad, wg, wm, bw,
                       ws, rows_pad, chunks_total, zb, pl.nA, pl.sB, pl.cpsB, pl.rowB0, pl.rowsB, tab1);
 }
 
@@ -1142,7 +1230,7 @@ void gemm_i8(const uint8_t *packed, size_t pitch, const int8_t *Qg, const int8_t
    if (tiled && !two && mode != I8_NO_MISSING) throw Error(-1, "gemm_i8: the one-operand kernels of both matrices read the row-major layout only");
    if (tiled && (pitch % 64 || k_pad > 4 * pitch)) throw Error(-1, "gemm_i8: a band-tiled copy has whole 64-byte chunks per row");
    if (e_only && (mode != I8_NO_MISSING || two)) throw Error(-1, "gemm_i8: e_only goes with the one-matrix kernel");
-   const I8Shape sh = i8_shape(S, b, two, mode);
+   const I8Shape sh = i8_shape(S, b, two, mode, rows_pad);
    const int bw = i8_bw(b); // Q holds gemm_i8_nsc_pad(S, b) rows; rows >= S*b are zero and carry zero weights
    const I8Plan pl = i8_plan(rows_pad, k_pad, sh, bw);
    const int chunks_total = (int)(k_pad / sh.kc);
@@ -1192,7 +1280,11 @@ void gemm_i8(const uint8_t *packed, size_t pitch, const int8_t *Qg, const int8_t
          else
             FPCA_I8_K3_NT(I8_FULL)
       } else if (mode == I8_NO_MISSING) {
-         if (sh.half && sh.nt == 2)
+         if (sh.rows == 512 && sh.half) // 8 waves, 512 rows (i8_tile_rows)
+            launch_i8<I8Cfg<false, 2, 4, 8, 1, 256, 1, I8_NO_MISSING, true, TL>>(FPCA_I8_ARGS);
+         else if (sh.rows == 512)
+            launch_i8<I8Cfg<false, 2, 2, 8, 1, 256, 1, I8_NO_MISSING, false, TL>>(FPCA_I8_ARGS);
+         else if (sh.half && sh.nt == 2)
             launch_i8<I8Cfg<false, 2, 2, 4, 1, 256, 1, I8_NO_MISSING, true, TL>>(FPCA_I8_ARGS);
          else if (sh.half)
             launch_i8<I8Cfg<false, 2, 4, 4, 1, 256, 1, I8_NO_MISSING, true, TL>>(FPCA_I8_ARGS);
