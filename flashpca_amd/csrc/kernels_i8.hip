@@ -477,7 +477,7 @@ void i8_dequant_rows(const int8_t *Qrm, uint64_t rows, int b, int S, const Slice
 //   Workgroup = 4 waves, ONE wave per SIMD with the whole 512-register budget (up to 256 accumulator AGPRs), arranged
 //   WR x WC; a wave owns MT x NT tiles of 32x32 of both matrices (2 MT NT <= 16 accumulators).  (Or 8 x 1 waves, two per SIMD with
 //   256 registers each, around the same operand tiles -- the G.M-alone kernel at 512 rows, see I8Cfg and i8_tile_rows.)  Operand tiles
-//   [WC NT 32 columns][KC k] are double-buffered in LDS (row stride KC + 16 B: the 16 lanes of a ds_read_b128 group hit
+//   [WC NT 32 columns][KC k] are double-buffered (8 waves: three buffers, I8Cfg::NBUF) in LDS (row stride KC + 16 B: the 16 lanes of a ds_read_b128 group hit
 //   distinct banks); the packed words go straight from global memory to the registers of the lane that decodes them.
 //   Decode: a lane's dword w holds 16 codes; (w >> 2q) & 0x03030303 leaves codes q, q+4, q+8, q+12 in the four bytes
 //   and v_perm_b32 with the code as selector looks G.M / M up in a 4-byte table -- 4 VALU ops per operand dword
@@ -543,7 +543,7 @@ enum { I8_FULL = 0, I8_SKIP_EMPTY = 1, I8_NO_MISSING = 2 };
 
 // What the main loop costs, measured with parts of it compiled out (profiles/r04_i8_ablation_2tile.txt; the 7-tile kernel in
 // docs/history/DESIGN_r04.md §7c): the operand stream's L2 misses cost nothing, the packed words cost their HBM energy rather than
-// their latency (issuing them further ahead ran slower), and at 7 tiles the per-chunk barrier costs nothing.  With an all-zero
+// their latency (issuing them further ahead ran slower), and at 7 tiles the per-chunk barrier costs nothing (under 8 waves it cost 150-170 cycles per chunk: I8Cfg::NBUF).  With an all-zero
 // fp64 operand (same instructions, same traffic) the same launch takes 7.07 ms instead of 9.04: the kernel follows the bare MFMA
 // stream's power curve.
 // HALF: the last of the NT column tiles has only 16 columns (S b = 112 for b = 16, S = 7: 3.5 tiles).  As a 32-wide tile half
@@ -578,6 +578,11 @@ struct I8Cfg {
    static constexpr int LDQH = LDQ + (HALF ? 16 : 0);   // row stride of the remainder tile's rows
    static constexpr int QTILE = COLS * LDQ + (HALF ? 16 * 16 : 0); // bytes of one operand tile
    static constexpr int STAGE = NQ * QTILE;
+   // stage buffers.  8 waves: both waves of a SIMD stand at the chunk barrier together and nothing covers the cold start behind it (LDS
+   // round trip + decode before the first MFMA), so a THIRD buffer lets a wave fetch the first operand fragment of chunk c + 1 BEFORE
+   // the barrier that ends chunk c: the tile of c + 1 was stored during c - 1 and published one barrier ago, the barrier of c
+   // publishes c + 2.  (One wave per SIMD, twice the MFMAs per chunk and wave: the barrier measured free -- two buffers.)
+   static constexpr int NBUF = WR == 8 ? 3 : 2;
    static constexpr int SEGS = KC / 16, RSTEP = THREADS / SEGS; // 16-byte segments per row; rows covered by one piece of every thread
    // HALF with 512 threads: the 16 rows of the remainder tile are half a piece -- every thread takes 8 bytes of them instead
    // (512 x 8 B = 16 rows of KC = 256), so that all waves issue the same loads and count the same waits
@@ -588,9 +593,9 @@ struct I8Cfg {
    static constexpr int PW = KC / 128;                  // 16-byte packed pieces per lane per m-tile (lane half = KC/2 k)
    static constexpr int NSTEP = KS * MT * G;            // micro-steps per chunk
    static constexpr int H = NSTEP / 2;
-   // dynamic LDS: the double-buffered operand tiles; the epilogue reuses it for WAVES x NT dumped tiles + the weights
+   // dynamic LDS: the NBUF operand tiles; the epilogue reuses it for WAVES x NT dumped tiles + the weights
    static constexpr int LDS_EPI = WAVES * NT * 4096 + 2 * WC * NT * 32 * 8;
-   static constexpr int LDS_NEED = (2 * STAGE > LDS_EPI) ? 2 * STAGE : LDS_EPI;
+   static constexpr int LDS_NEED = (NBUF * STAGE > LDS_EPI) ? NBUF * STAGE : LDS_EPI;
    // The narrowest column block (2 tiles: 136 registers, 34 KB) would fit three workgroups per CU; measured at 500,000 x
    // 100,000 (scripts/r4_narrow_probe.sh, GEMM kernels K2 / K3): three per CU 4.61 / 4.74 ms, two 4.31 / 4.39, one 5.20 / 5.74 --
    // so it asks for enough LDS to be two (the wider blocks are two or one by their registers: 224+ of 512).
@@ -634,6 +639,7 @@ __global__ __launch_bounds__(C::THREADS, 1) void k_gemm_i8(const uint8_t *__rest
    constexpr int MT = C::MT, NT = C::NT, NQ = C::NQ, KC = C::KC, NP = C::NP, NP1 = C::NP1, NSTEP = C::NSTEP, LDQ = C::LDQ,
                  H = C::H, G = C::G, PW = C::PW, NPK = MT * PW, NTF = C::NTF;
    constexpr bool HALF = C::HALF;
+   constexpr int NBUF = C::NBUF;
    constexpr int AMASK = HALF ? 3 : 1; // decoded genotype fragments kept alive: 2, or 4 (even AND odd k-step of both m-tiles)
    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -736,18 +742,40 @@ __global__ __launch_bounds__(C::THREADS, 1) void k_gemm_i8(const uint8_t *__rest
 
    constexpr std::integral_constant<int, NPK> after_p{};
    constexpr std::integral_constant<int, 0> after_none{};
+   // three buffers: the prologue stages chunks c_begin and c_begin + 1 (clamped, like every staged chunk, to the unit's last one)
+   const int c_second = (c_begin + 1 < c_end) ? c_begin + 1 : c_begin;
    if (idle) {
-      // the staging alone, chunk by chunk, barrier for barrier what the working waves do below
+      // the staging alone, chunk by chunk, barrier for barrier and buffer for buffer what the working waves do below
       static_for<NP>([&](auto rr) { issue_q(rr, c_begin); });
       static_for<NP>([&](auto rr) { store_q(rr, smem + qdst, after_none); });
+      if constexpr (NBUF == 3) {
+         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // the stores have read their registers
+         static_for<NP>([&](auto rr) { issue_q(rr, c_second); });
+         static_for<NP>([&](auto rr) { store_q(rr, smem + C::STAGE + qdst, after_none); });
+      }
       __syncthreads();
+      int wbuf = NBUF - 1; // buffer staged during the chunk: (c - c_begin + NBUF - 1) % NBUF
       for (int c = c_begin; c < c_end; c++) {
-         const int cn = (c + 1 < c_end) ? c + 1 : c;
-         unsigned char *wst = smem + (size_t)(((c - c_begin) & 1) ^ 1) * C::STAGE + qdst;
+         const int cn = (c + NBUF - 1 < c_end) ? c + NBUF - 1 : c_end - 1;
+         unsigned char *wst = smem + (size_t)wbuf * C::STAGE + qdst;
          static_for<NP>([&](auto rr) { issue_q(rr, cn); });
          static_for<NP>([&](auto rr) { store_q(rr, wst, after_none); });
          __syncthreads();
+         wbuf = wbuf + 1 == NBUF ? 0 : wbuf + 1;
       }
+   } else if constexpr (NBUF == 3) {
+      // prologue: chunks c_begin and c_begin + 1
+      static_for<NP>([&](auto rr) { issue_q(rr, c_begin); });
+      static_for<NP>([&](auto rr) { store_q(rr, smem + qdst, after_none); });
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // the stores have read their registers
+      static_for<NP>([&](auto rr) { issue_q(rr, c_second); });
+      issue_p(pk, c_begin);
+      static_for<NP>([&](auto rr) { store_q(rr, smem + C::STAGE + qdst, after_p); });
+#pragma unroll
+      for (int m = 0; m < MT; m++)
+#pragma unroll
+         for (int h = 0; h < PW; h++) vm_wait<0>(pk[m][h]);
+      __syncthreads();
    } else {
       // prologue: chunk c_begin
       static_for<NP>([&](auto rr) { issue_q(rr, c_begin); });
@@ -760,55 +788,76 @@ __global__ __launch_bounds__(C::THREADS, 1) void k_gemm_i8(const uint8_t *__rest
       __syncthreads();
    }
 
+   // micro-step s -> (ks, m, g); operand fragments are keyed by (ks, g), genotype fragments by (ks, m)
+   constexpr int NG = (NT + G - 1) / G; // n-tiles per group (the last group may be shorter)
+   v4i bq[2][NQ][NG];
+   v4i bqh = {0, 0, 0, 0}, bqh2 = {0, 0, 0, 0}; // HALF: the 16-column operand(s) of the current pair of k-steps
+   v4i ag[AMASK + 1], am[AMASK + 1]; // decoded genotype fragments, index = micro-step parity (HALF: (k-step parity, m))
+   bool enz[AMASK + 1];             // ... and whether the E fragment has any nonzero at all (wave-uniform)
+   constexpr std::integral_constant<int, 0> i0{};
+   auto read_b = [&](auto kk, auto gg, auto par, uint32_t aQ, uint32_t aQ2, uint32_t aQh) { // the stage buffer's addresses
+      constexpr int ks = decltype(kk)::value, g = decltype(gg)::value, p = decltype(par)::value;
+      static_for<NG>([&](auto jj) {
+         constexpr int j = decltype(jj)::value, n = g * NG + j;
+         if constexpr (n < NTF) {
+            bq[p][0][j] = lds_read16<32 * n * LDQ + ks * 16>(aQ);
+            if constexpr (TWO) bq[p][NQ - 1][j] = lds_read16<32 * n * LDQ + ks * 16>(aQ2);
+         }
+      });
+      if constexpr (HALF && (ks & 1) == 1) { // both k-steps of the pair in one read
+         bqh = lds_read16<(ks >> 1) * 32>(aQh);
+         if constexpr (TWO) bqh2 = lds_read16<(ks >> 1) * 32 + C::QTILE>(aQh);
+      }
+   };
+   auto wait_b = [&](auto gg, auto par) {
+      constexpr int g = decltype(gg)::value, p = decltype(par)::value;
+      static_for<NG>([&](auto jj) {
+         constexpr int j = decltype(jj)::value, n = g * NG + j;
+         if constexpr (n < NTF) {
+            if constexpr (TWO)
+               lds_wait(bq[p][0][j], bq[p][NQ - 1][j]);
+            else
+               lds_wait(bq[p][0][j]);
+         }
+      });
+      if constexpr (HALF) {
+         if constexpr (TWO)
+            lds_wait(bqh, bqh2);
+         else
+            lds_wait(bqh);
+      }
+   };
+   // Three buffers: chunk c reads buffer i % 3 (i = c - c_begin), stages chunk min(c + 2, c_end - 1) into buffer (i + 2) % 3 -- the one
+   // read during chunk c - 1, which every wave left before the barrier that ended c - 1 -- and, in its last micro-step, fetches the first
+   // operand fragments of chunk c + 1 from buffer (i + 1) % 3 (stored during c - 1, published by that same barrier) and decodes its
+   // first genotype fragment from the packed words that are one chunk ahead anyway: behind the barrier the first MFMAs find their
+   // operands in registers.  The barrier that ends chunk c publishes the tile of c + 2 and says that every wave has left buffer i % 3,
+   // which chunk c + 1 overwrites in its second half.  A clamped re-stage (the last two chunks of a unit; a unit of one chunk) lands in
+   // a buffer that nobody reads any more; the fetch behind the last chunk reads a published buffer and is dropped.
+   int buf = 0; // (three buffers: i % 3, stepped at the end of the chunk)
+   if constexpr (NBUF == 3) {
+      if (!idle) { // the first fragments of the first chunk
+         read_b(i0, i0, i0, aQ0, aQ0 + C::QTILE, aQh0);
+         enz[0] = i8_decode<MODE>(pk[0][0][0], ag[0], am[0], tab1);
+         wait_b(i0, i0);
+         __builtin_amdgcn_sched_barrier(0);
+      }
+   }
    for (int c = idle ? c_end : c_begin; c < c_end; c++) {
-      const int buf = (c - c_begin) & 1;
+      if constexpr (NBUF == 2) buf = (c - c_begin) & 1;
       const int cn = (c + 1 < c_end) ? c + 1 : c; // the last chunk re-stages itself (branch-free pipeline)
       const uint32_t aQ = aQ0 + (uint32_t)buf * C::STAGE, aQ2 = aQ + C::QTILE;
-      unsigned char *wst = smem + (size_t)(buf ^ 1) * C::STAGE + qdst;
-
-      // micro-step s -> (ks, m, g); operand fragments are keyed by (ks, g), genotype fragments by (ks, m)
-      constexpr int NG = (NT + G - 1) / G; // n-tiles per group (the last group may be shorter)
-      v4i bq[2][NQ][NG];
-      v4i bqh = {0, 0, 0, 0}, bqh2 = {0, 0, 0, 0}; // HALF: the 16-column operand(s) of the current pair of k-steps
-      v4i ag[AMASK + 1], am[AMASK + 1]; // decoded genotype fragments, index = micro-step parity (HALF: (k-step parity, m))
-      bool enz[AMASK + 1];             // ... and whether the E fragment has any nonzero at all (wave-uniform)
+      const int bufw = NBUF == 2 ? buf ^ 1 : (buf == 0 ? 2 : buf - 1), bufn = buf == NBUF - 1 ? 0 : buf + 1; // staged now; read next
+      unsigned char *wst = smem + (size_t)bufw * C::STAGE + qdst;
+      const int cq = NBUF == 2 ? cn : ((c + 2 < c_end) ? c + 2 : c_end - 1); // the chunk whose operand tile is staged
       const uint32_t aQh = aQh0 + (uint32_t)buf * C::STAGE;
-      auto read_b = [&](auto kk, auto gg, auto par) {
-         constexpr int ks = decltype(kk)::value, g = decltype(gg)::value, p = decltype(par)::value;
-         static_for<NG>([&](auto jj) {
-            constexpr int j = decltype(jj)::value, n = g * NG + j;
-            if constexpr (n < NTF) {
-               bq[p][0][j] = lds_read16<32 * n * LDQ + ks * 16>(aQ);
-               if constexpr (TWO) bq[p][NQ - 1][j] = lds_read16<32 * n * LDQ + ks * 16>(aQ2);
-            }
-         });
-         if constexpr (HALF && (ks & 1) == 1) { // both k-steps of the pair in one read
-            bqh = lds_read16<(ks >> 1) * 32>(aQh);
-            if constexpr (TWO) bqh2 = lds_read16<(ks >> 1) * 32 + C::QTILE>(aQh);
-         }
-      };
-      auto wait_b = [&](auto gg, auto par) {
-         constexpr int g = decltype(gg)::value, p = decltype(par)::value;
-         static_for<NG>([&](auto jj) {
-            constexpr int j = decltype(jj)::value, n = g * NG + j;
-            if constexpr (n < NTF) {
-               if constexpr (TWO)
-                  lds_wait(bq[p][0][j], bq[p][NQ - 1][j]);
-               else
-                  lds_wait(bq[p][0][j]);
-            }
-         });
-         if constexpr (HALF) {
-            if constexpr (TWO)
-               lds_wait(bqh, bqh2);
-            else
-               lds_wait(bqh);
-         }
-      };
-      read_b(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
-      enz[0] = i8_decode<MODE>(pk[0][0][0], ag[0], am[0], tab1);
-      wait_b(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
-      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (NBUF == 2) {
+         if constexpr (HALF) bqh = bqh2 = (v4i){0, 0, 0, 0};
+         read_b(i0, i0, i0, aQ, aQ2, aQh);
+         enz[0] = i8_decode<MODE>(pk[0][0][0], ag[0], am[0], tab1);
+         wait_b(i0, i0);
+         __builtin_amdgcn_sched_barrier(0);
+      }
 
       static_for<NSTEP>([&](auto ss) {
          constexpr int s = decltype(ss)::value;
@@ -821,7 +870,7 @@ __global__ __launch_bounds__(C::THREADS, 1) void k_gemm_i8(const uint8_t *__rest
          // --- staging of chunk cn: loads in the first half, packed words at the half-way mark, LDS stores in the second
          if constexpr (s < H) {
             static_for<(s + 1) * NP / H - s * NP / H>([&](auto jj) {
-               issue_q(std::integral_constant<int, s * NP / H + decltype(jj)::value>{}, cn);
+               issue_q(std::integral_constant<int, s * NP / H + decltype(jj)::value>{}, cq);
             });
          }
          if constexpr (s == H - 1) issue_p(pkn, cn);
@@ -832,7 +881,21 @@ __global__ __launch_bounds__(C::THREADS, 1) void k_gemm_i8(const uint8_t *__rest
          }
          // --- operand fragments of the next micro-step
          if constexpr (bkey1 != bkey)
-            read_b(std::integral_constant<int, ks1>{}, std::integral_constant<int, g1>{}, std::integral_constant<int, (bkey1 & 1)>{});
+            read_b(std::integral_constant<int, ks1>{}, std::integral_constant<int, g1>{}, std::integral_constant<int, (bkey1 & 1)>{}, aQ, aQ2, aQh);
+         // (three buffers, last micro-step: the packed words of the next chunk have had half a chunk to arrive; fragment registers
+         // bq[0] and ag[0] / am[0] were last used one k-step ago)
+         constexpr bool ahead = NBUF == 3 && last;
+         if constexpr (ahead) {
+            static_assert(G == 1 && ((NSTEP / MT - 1) & 1) == 1 && ((NSTEP - 1) & AMASK) != 0, "the last micro-step leaves bq[0] and ag[0] free");
+#pragma unroll
+            for (int mm = 0; mm < MT; mm++)
+#pragma unroll
+               for (int h = 0; h < PW; h++) {
+                  vm_wait<0>(pkn[mm][h]);
+                  pk[mm][h] = pkn[mm][h];
+               }
+            read_b(i0, i0, i0, aQ0 + (uint32_t)bufn * C::STAGE, aQ0 + (uint32_t)bufn * C::STAGE + C::QTILE, aQh0);
+         }
          // --- this micro-step's MFMAs, the next micro-step's decode in their shadow
          static_for<NG>([&](auto jj) {
             constexpr int j = decltype(jj)::value, n = g * NG + j;
@@ -843,6 +906,7 @@ __global__ __launch_bounds__(C::THREADS, 1) void k_gemm_i8(const uint8_t *__rest
             }
             if constexpr (j == 0 && akey1 != akey)
                enz[akey1 & AMASK] = i8_decode<MODE>(pk[m1][ks1 >> 2][ks1 & 3], ag[akey1 & AMASK], am[akey1 & AMASK], tab1);
+            if constexpr (j == 0 && ahead) enz[0] = i8_decode<MODE>(pk[0][0][0], ag[0], am[0], tab1);
          });
          if constexpr (HALF && (ks & 1) == 1) {
             // the 16 remaining columns over k-steps ks - 1 and ks: row group r of the even / odd fragment = rows 16 (r & 1) ..
@@ -883,15 +947,29 @@ __global__ __launch_bounds__(C::THREADS, 1) void k_gemm_i8(const uint8_t *__rest
             wait_b(std::integral_constant<int, g1>{}, std::integral_constant<int, (bkey1 & 1)>{});
             __builtin_amdgcn_sched_barrier(0);
          }
-      });
-#pragma unroll
-      for (int m = 0; m < MT; m++)
-#pragma unroll
-         for (int h = 0; h < PW; h++) {
-            vm_wait<0>(pkn[m][h]);
-            pk[m][h] = pkn[m][h];
+         if constexpr (ahead) { // lgkmcnt(0): the fetched fragments are here AND this wave's stores of the chunk are in LDS
+            wait_b(i0, i0);
+            __builtin_amdgcn_sched_barrier(0);
          }
-      __syncthreads();
+      });
+      if constexpr (NBUF == 3) {
+         // every load of the chunk has been waited for (the packed words last) and lgkmcnt is zero: the bare barrier, without the
+         // vmcnt(0) lgkmcnt(0) that __syncthreads() puts in front of it
+         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+         __builtin_amdgcn_s_barrier();
+         asm volatile("" ::: "memory");
+         __builtin_amdgcn_sched_barrier(0);
+         buf = bufn;
+      } else {
+#pragma unroll
+         for (int m = 0; m < MT; m++)
+#pragma unroll
+            for (int h = 0; h < PW; h++) {
+               vm_wait<0>(pkn[m][h]);
+               pk[m][h] = pkn[m][h];
+            }
+         __syncthreads();
+      }
    }
 
    // epilogue: the slices are recombined here, per split and column block, into fp64 partial sums -- virtual column
@@ -1145,7 +1223,10 @@ static bool i8_verbose()
 
 static I8Plan i8_plan(uint64_t rows_pad, uint64_t k_pad, const I8Shape &sh, int bw)
 {
-   static const char *env_s = FPCA_TEST_ENV("FPCA_I8_SPLITS"); // force plain split-K with this factor
+   // force plain split-K with this factor (test builds), down to units of ONE chunk: a forced factor is not held to the four chunks per
+   // split of the plan's own choices
+   static const char *env_s = FPCA_TEST_ENV("FPCA_I8_SPLITS");
+   const int forced = (env_s && atoi(env_s) > 0) ? std::min(atoi(env_s), 16) : 0;
    const int ncu = i8_ncu();
    const int rtiles = (int)((rows_pad + (sh.rows == 512 ? 511 : 0)) / sh.rows), rtl = (rtiles + 7) / 8, ids = 8 * rtl * sh.zb;
    const int chunks = (int)(k_pad / sh.kc);
@@ -1157,10 +1238,10 @@ static I8Plan i8_plan(uint64_t rows_pad, uint64_t k_pad, const I8Shape &sh, int 
    const int nA_full = ids / ncu * ncu;
    for (int pass = 0; pass < 2; pass++) {
       const int nA = pass == 0 ? 0 : (nA_full == ids ? ids - ncu : nA_full);
-      if (pass == 1 && (nA <= 0 || (env_s && atoi(env_s) > 0))) break;
+      if (pass == 1 && (nA <= 0 || forced)) break;
       const int nB = ids - nA;
-      for (int s = 1; s <= 16 && (s == 1 || s * 4 <= chunks); s++) {
-         if (pass == 0 && env_s && atoi(env_s) > 0 && s != std::min(atoi(env_s), std::max(chunks / 4, 1))) continue;
+      for (int s = 1; s <= 16 && (s == 1 || (forced ? s <= chunks : s * 4 <= chunks)); s++) {
+         if (pass == 0 && forced && s != std::min(forced, std::max(chunks, 1))) continue;
          const int cps = (chunks + s - 1) / s;
          const double tA = (double)(nA / ncu) * (chunks * t_chunk + t_seg);
          const double tB = (double)((nB * s + ncu - 1) / ncu) * (cps * t_chunk + t_seg);
