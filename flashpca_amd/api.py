@@ -198,6 +198,43 @@ class Context:
         check(lib().fpca_debug_snp_subset_bench(self.h, _p(k8), int(reps), C.byref(ms), C.byref(by)))
         return ms.value, by.value
 
+    # ---- LD pruning --------------------------------------------------------------------------------
+    def ld_band(self, snp0, nsnp, span):
+        """fpca_ld_band: the nsnp x span array of pairwise-complete r2 between SNP snp0 + i and SNP snp0 + i + d (column d - 1); NaN past
+        the end of the range, where a pair shares no call, and where a SNP is constant on the shared calls."""
+        snp0, nsnp, span = int(snp0), int(nsnp), int(span)
+        if snp0 < 0 or nsnp < 0 or not 0 <= span < 2 ** 32:
+            raise ValueError("snp0, nsnp and span are non-negative (span below 2^32)")
+        out = np.empty((max(nsnp, 1), max(span, 1)), dtype=np.float64)  # (a zero-sized request still reaches the library's refusal)
+        check(lib().fpca_ld_band(self.h, snp0, nsnp, span, _p(out)))
+        return out[:nsnp, :span]
+
+    def ld_prune(self, window=1000, step=50, r2=0.05, chrom=None, keep=None):
+        """fpca_ld_prune: the boolean mask of the SNPs a PLINK-1.9-style --indep-pairwise window step r2 keeps (windows and steps in
+        SNPs), among those of `keep` (a mask or an index array; None: all).  chrom: one integer code per SNP, a chromosome being a
+        maximal run of equal codes (None: one chromosome)."""
+        window, step = int(window), int(step)
+        if not (0 <= window < 2 ** 32 and 0 <= step < 2 ** 32):
+            raise ValueError("window and step are SNP counts in 0 .. 2^32 - 1")
+        k8 = np.ascontiguousarray(np.ones(self.P, dtype=bool) if keep is None else _snp_mask(keep, self.P), dtype=np.uint8)
+        c32 = None
+        if chrom is not None:
+            c32 = np.ascontiguousarray(chrom, dtype=np.uint32)
+            if c32.shape != (self.P,):
+                raise ValueError("chrom must have one entry per SNP (%d), it has shape %s" % (self.P, c32.shape))
+        n = C.c_uint64(0)
+        check(lib().fpca_ld_prune(self.h, _p(c32), window, step, float(r2), _p(k8), C.byref(n)))
+        out = k8 != 0
+        assert int(out.sum()) == n.value
+        return out
+
+    def bench_ld(self, span, reps=5):
+        """fpca_bench_ld: (milliseconds of each of `reps` launches of the bitmap kernel over all SNPs, int8 MACs one launch issues)."""
+        ms = np.zeros(int(reps), dtype=np.float64)
+        macs = C.c_double(0)
+        check(lib().fpca_bench_ld(self.h, int(span), int(reps), _p(ms), C.byref(macs)))
+        return ms, macs.value
+
     def set_total_snps(self, P_total):
         check(lib().fpca_set_total_snps(self.h, int(P_total)))
         self.P_total = int(P_total)
@@ -452,7 +489,7 @@ class Context:
 
 
 def flashpca(X, ndim=10, stand="binom2", divisor="p", maxiter=500, tol=1e-6, do_loadings=False, return_scale=True,
-             device=0, verbose=False, accum="auto", keep=None, snps=None, maf=0.0, geno=1.0, **solver_kw):
+             device=0, verbose=False, accum="auto", keep=None, snps=None, maf=0.0, geno=1.0, ld=None, **solver_kw):
     """PCA of a PLINK fileset; mirrors flashpca() of the reference's R package for the PLINK-prefix input
     (flashpcaR/R/flashpca.R:99-204 -> flashpca_plink_internal, flashpcaR/src/flashpca.cpp:96-197).
 
@@ -465,6 +502,8 @@ def flashpca(X, ndim=10, stand="binom2", divisor="p", maxiter=500, tol=1e-6, do_
     --geno on the uploaded matrix (minor-allele frequency >= maf, missing-call rate <= geno; both over all samples, so not together
     with keep=).  PLINK input only.  The selected SNPs are compacted once on the device and the PCA runs on them: loadings, center and
     scale have one row per kept SNP, divisor "p" is the kept count, and the result gains `snps_kept`, the mask over the .bim rows.
+    ld: (window, step, r2) -- LD pruning in the style of PLINK's --indep-pairwise, windows and steps in SNPs, chromosomes from the .bim,
+    applied to the survivors of snps / maf / geno (Context.ld_prune); r2 is over all samples, so not together with keep=.
     Returns values, vectors, projection, loadings, center, scale, pve.
     """
     if divisor not in DIVISOR:
@@ -475,6 +514,12 @@ def flashpca(X, ndim=10, stand="binom2", divisor="p", maxiter=500, tol=1e-6, do_
     if qc and keep is not None:
         raise ValueError("maf / geno cannot be combined with keep: PLINK takes these frequencies over the kept samples, the counts here "
                          "are those of all samples")
+    if ld is not None:
+        ld = _ld_args(ld)
+        if not isinstance(X, str):
+            raise ValueError("ld prunes the SNPs of a PLINK fileset; it does not apply to a numeric matrix")
+        if keep is not None:
+            raise ValueError("ld cannot be combined with keep: PLINK takes r2 over the kept samples, r2 here is over all samples")
     if isinstance(X, str):
         if stand not in STANDARDISE:
             raise ValueError("stand must be one of %s" % sorted(STANDARDISE))  # R: match.arg
@@ -485,12 +530,9 @@ def flashpca(X, ndim=10, stand="binom2", divisor="p", maxiter=500, tol=1e-6, do_
             raise ValueError("stand must be one of %s" % sorted(_lib.STANDARDISE_DENSE))
         ctx = Context.from_dense(np.asarray(X, dtype=np.float64), stand=stand, device=device)
     snps_kept = None
-    if snps is not None or qc:
-        with ctx as full:
-            snps_kept = np.ones(full.P, dtype=bool) if snps is None else _snp_mask(snps, full.P)
-            if qc:
-                snps_kept = full.snp_qc(maf=maf, geno=geno, keep=snps_kept)
-            ctx = full.snp_subset(snps_kept)  # one compaction of the combined mask; the source is closed on the way out
+    if snps is not None or qc or ld is not None:
+        with ctx as full:  # (the source is closed on the way out)
+            ctx, snps_kept = _select_snps(full, X, snps, qc, maf, geno, ld)
     with ctx:
         if keep is not None:
             keep = np.asarray(keep)
@@ -524,7 +566,7 @@ def _is_012(A):
     return bool(np.all(np.isin(A[~np.isnan(A)], (0.0, 1.0, 2.0))))
 
 
-def ucca(X, Y, standx="binom2", standy="binom2", check_geno=True, check_fam=True, verbose=False, device=0, snps=None):
+def ucca(X, Y, standx="binom2", standy="binom2", check_geno=True, check_fam=True, verbose=False, device=0, snps=None, ld=None):
     """Per-SNP canonical correlation (ANOVA of all phenotypes on each SNP, plink.multivariate); mirrors ucca() of the reference's R
     package (flashpcaR/R/ucca.R): same arguments and defaults, its stop() checks raised as ValueError with R's wording.
 
@@ -532,6 +574,7 @@ def ucca(X, Y, standx="binom2", standy="binom2", check_geno=True, check_fam=True
     standardisations).  Y: N x k phenotypes (NaN = missing, mean-imputed).
     snps (PLINK input only): a boolean mask over the .bim rows or an array of unique row indices, e.g. from snp_filter(); the scan
     runs on those SNPs, result and snp_ids have one row per kept SNP, and the mask comes back as snps_kept.
+    ld (PLINK input only): (window, step, r2), LD pruning of those SNPs as in flashpca(ld=); snps_kept is the final mask.
     Returns result (P x 3: R, Fstat, P), npheno and, for the PLINK input, snp_ids in .bim order (ucca_plink_internal,
     flashpcaR/src/flashpca.cpp:275-334).
     """
@@ -541,6 +584,10 @@ def ucca(X, Y, standx="binom2", standy="binom2", check_geno=True, check_fam=True
     standy = _match_arg("standy", standy)
     if snps is not None and not isinstance(X, str):
         raise ValueError("snps selects SNPs of a PLINK fileset; it does not apply to a numeric matrix")
+    if ld is not None:
+        ld = _ld_args(ld)
+        if not isinstance(X, str):
+            raise ValueError("ld prunes the SNPs of a PLINK fileset; it does not apply to a numeric matrix")
     try:
         Y = np.asarray(Y, dtype=np.float64)
     except (TypeError, ValueError):
@@ -584,10 +631,9 @@ def ucca(X, Y, standx="binom2", standy="binom2", check_geno=True, check_fam=True
     else:
         ctx = Context.from_dense(X, stand=standx, device=device)
     snps_kept = None
-    if snps is not None:
+    if snps is not None or ld is not None:
         with ctx as full:
-            snps_kept = _snp_mask(snps, full.P)
-            ctx = full.snp_subset(snps_kept)
+            ctx, snps_kept = _select_snps(full, X, snps, False, 0.0, 1.0, ld)
     with ctx:
         if verbose:
             print("UCCA online mode, N=%d p=%d" % (ctx.N, ctx.P))
@@ -876,6 +922,60 @@ def snp_filter(prefix, extract=None, exclude=None, extract_ranges=None, exclude_
     if exclude_ranges is not None:
         mask &= ~in_ranges(exclude_ranges)
     return mask
+
+
+def _ld_args(ld):
+    try:
+        w, s, t = ld
+        w, s, t = int(w), int(s), float(t)
+    except (TypeError, ValueError):
+        raise ValueError("ld is (window, step, r2): two SNP counts and a threshold, found %r" % (ld,))
+    return w, s, t
+
+
+def _bim_chrom_codes(prefix):
+    """One integer per .bim row, equal for equal chromosome fields: fpca_ld_prune's chromosomes are the runs of equal codes."""
+    col = np.array([l.split()[0] for l in open(prefix + ".bim").read().splitlines() if l.strip()])
+    return np.unique(col, return_inverse=True)[1].astype(np.uint32)
+
+
+def _selection_mask(full, prefix, snps, qc, maf, geno, ld):
+    """The SNP selection of flashpca() / ucca() / ld_prune() on the uploaded fileset `full`, as a mask over the .bim rows: list filter,
+    QC filter, then LD pruning of the survivors."""
+    mask = np.ones(full.P, dtype=bool) if snps is None else _snp_mask(snps, full.P)
+    if qc:
+        mask = full.snp_qc(maf=maf, geno=geno, keep=mask)
+    if ld is None:
+        return mask
+    chrom = _bim_chrom_codes(prefix)
+    if chrom.shape != (full.P,):
+        raise ValueError("%s.bim has %d rows, the .bed holds %d SNPs" % (prefix, chrom.size, full.P))
+    if snps is None and not qc:  # nothing filtered before: the windows count the fileset's own SNPs, no first compaction
+        return full.ld_prune(*ld, chrom=chrom)
+    # the windows count the survivors of the earlier filters, as in PLINK: prune on their compaction (gone again before the caller
+    # compacts the final mask from the source: a gather of a gather is a gather)
+    with full.snp_subset(mask, accum="fp64") as mid:
+        kept = mid.ld_prune(*ld, chrom=chrom[mask])
+    mask = mask.copy()
+    mask[np.flatnonzero(mask)] = kept
+    return mask
+
+
+def _select_snps(full, prefix, snps, qc, maf, geno, ld):
+    """(a new Context holding the selected SNPs of `full`, compacted once from it; the mask over the .bim rows).  `full` stays open."""
+    mask = _selection_mask(full, prefix, snps, qc, maf, geno, ld)
+    return full.snp_subset(mask), mask
+
+
+def ld_prune(prefix, window=1000, step=50, r2=0.05, snps=None, maf=0.0, geno=1.0, device=0):
+    """LD pruning of a PLINK fileset on the GPU, in the style of `plink --indep-pairwise window step r2` (windows and steps in SNPs):
+    a boolean mask over the rows of prefix.bim.  snps / maf / geno as in flashpca(): they are applied first, and the windows count
+    their survivors.  Not byte-compatible with the plink binary (its window refill and its MAF epsilon differ in detail)."""
+    qc = not (maf <= 0 and geno >= 1)
+    ld = _ld_args((window, step, r2))
+    N = count_fam_rows(prefix + ".fam")
+    with Context.from_bed(prefix + ".bed", N, device=device, accum="fp64") as full:
+        return _selection_mask(full, prefix, snps, qc, maf, geno, ld)
 
 
 def project(X, loadings, orig_mean=None, orig_sd=None, ref_alleles=None, divisor="p", device=0, check_bim=True):

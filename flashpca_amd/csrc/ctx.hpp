@@ -15,6 +15,8 @@
 //   sample_mask.hip     fpca_set_sample_mask: statistics over the kept samples, the row mask of the operator's blocks, kept-row gather / scatter
 //   snp_subset.hip      fpca_snp_missing / fpca_snp_qc / fpca_create_snp_subset: the QC rule on K1's counts, the record gather that compacts
 //                       the kept SNPs into a new context
+//   ld_band.hip         fpca_ld_band / fpca_ld_prune: windowed pairwise r2 as a banded integer Gram of the packed matrix with itself
+//                       (k_ld_band, six exact int8 products per pair), the --indep-pairwise rule on the host
 // MI355X / gfx950 only; there is no CPU fallback anywhere in the library.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -313,6 +315,14 @@ void refuse_shard_while_masked(const fpca_ctx *c, const char *fn);           // 
 uint64_t snp_qc_rule(const double *mean, const uint32_t *n_missing, uint64_t N, uint64_t P, double min_maf, double max_missing, uint8_t *keep);
 std::vector<uint32_t> kept_indices(const uint8_t *keep, uint64_t P); // ascending record numbers of keep[j] != 0 (FPCA_EINVAL for P >= 2^32)
 void snp_qc_check_thresholds(const char *fn, double min_maf, double max_missing); // FPCA_EINVAL: NaN, min_maf > 0.5, max_missing < 0
+
+// ---- ld_band.hip ------------------------------------------------------------------------------------------
+// host only: the --indep-pairwise rule of fpca_ld_prune (include/fpca.h) on the band bitmap.  bits: P rows of `words` uint32, bit d - 1 of
+// row i set when r2(i, i + d) is above the threshold; totals [P][3] = calls, sum x, sum x^2 (monomorphic: calls * sum x^2 == (sum x)^2);
+// chrom may be null.  keep in and out; returns the number left non-zero.
+uint64_t ld_prune_rule(const uint32_t *bits, uint32_t words, uint64_t P, uint32_t window, uint32_t step, const uint64_t *totals,
+                       const double *maf, const uint32_t *chrom, uint8_t *keep);
+void ld_check_window(const char *fn, uint32_t window, uint32_t step); // FPCA_EINVAL: window < 2, step < 1, step > window
 
 // ---- download.hip -----------------------------------------------------------------------------------------
 // d_img: device, column-major N x ncols with leading dimension N -> host (ld) and, scaled per column, host2 (ld2); synchronises

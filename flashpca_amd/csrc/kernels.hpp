@@ -16,6 +16,13 @@ void fix_last_byte(uint8_t *packed, size_t pitch, uint64_t np, int valid_in_last
 // record gather (snp_subset.hip): dst[j][:] = src[idx[j]][:] over `pitch` bytes (a multiple of 16) for j < nrec; dst has the same pitch,
 // nothing at or after record nrec is written
 void gather_records(const uint8_t *src, size_t pitch, const uint32_t *idx, uint64_t nrec, uint8_t *dst, hipStream_t stream);
+// LD band (ld_band.hip).  ld_totals: tot[rec][4] = (sum x, sum x^2, codes "01" = missing calls + pad samples, 0) over the `pitch` bytes
+// of records [0, nrec).  ld_band: every pair i in [i0, i0 + ni), j in (i, min(i + span, jend - 1)] of records of `packed`; r2 != null:
+// r2[(i - i0) * span + (j - i - 1)] = the statistic (fp64); else bit (j - i - 1) of the row of `words` uint32 words of record i - i0 is
+// OR-ed into bits (zeroed by the caller) when the statistic is above thr.  npad = 4 pitch - N; jend <= records allocated.
+void ld_totals(const uint8_t *packed, size_t pitch, uint64_t nrec, uint32_t *tot, hipStream_t stream);
+void ld_band(const uint8_t *packed, size_t pitch, const uint32_t *tot, uint32_t npad, uint64_t i0, uint64_t ni, uint64_t jend, uint32_t span,
+             double *r2, uint32_t *bits, uint32_t words, double thr, bool force_general, hipStream_t stream);
 
 // K1: per-SNP code counts -> mean, sd, lookup table (by raw PLINK code), sum of squares
 //   lut [P_pad][4], mean/sd/sumsq [P_pad]; rows >= P_g untouched (must be pre-zeroed)

@@ -203,6 +203,33 @@ int fpca_snp_missing(fpca_ctx *ctx, uint32_t *n_missing);
 int fpca_snp_qc(fpca_ctx *ctx, double min_maf, double max_missing, uint8_t *keep, uint64_t *n_kept);
 int fpca_create_snp_subset(fpca_ctx **out, fpca_ctx *src, const uint8_t *keep, int accum);
 
+/* LD pruning: windowed pairwise r2 between the SNPs of the resident matrix, on the int8 matrix cores, and a PLINK-1.9-style
+ * --indep-pairwise rule on top of it.  The mask it leaves feeds fpca_create_snp_subset like any other.
+ *   The statistic, for SNPs i < j, dosage x in {0,1,2}, over the samples called at BOTH SNPs (pairwise-complete):
+ *      n = #samples, sx = sum x_i, sy = sum x_j, sxy = sum x_i x_j, sxx = sum x_i^2, syy = sum x_j^2     (exact integers)
+ *      c = n sxy - sx sy, vx = n sxx - sx^2, vy = n syy - sy^2                                           (int64, exact)
+ *      r2 = ((double)c * (double)c) / ((double)vx * (double)vy)        (two multiplies and one divide, each correctly rounded)
+ *   0 / 0 is NaN (no shared call, or a SNP constant on the shared calls); a NaN is never above a threshold.
+ *   fpca_ld_band   r2[nsnp][span], row-major: r2[i][d - 1] is the statistic of SNPs snp0 + i and snp0 + i + d, d = 1 .. span; NaN where
+ *                  i + d >= nsnp.  FPCA_EINVAL when the buffer would exceed 1 GiB (both sizes in the message).
+ *   fpca_ld_prune  keep[P_g] in and out, as for fpca_snp_qc: an entry that is 0 stays 0; *n_kept (may be NULL) = entries left non-zero.
+ *                  Positions are record numbers within a chromosome; a chromosome is a maximal run of equal values of chrom[P_g] (NULL:
+ *                  one chromosome).  Windows start at positions 0, step, 2 step, ... of the chromosome and cover `window` positions; the
+ *                  window that reaches the chromosome's end is its last.  SNPs with keep == 0 on entry, and SNPs that are monomorphic over
+ *                  their own calls (which includes "no call at all") -- these are set to 0 first --, occupy positions but are never
+ *                  compared.  Within a window, for i ascending and still kept, for j > i ascending and still kept with r2(i, j) > r2:
+ *                  when maf_i < maf_j (strictly; maf as fpca_snp_qc computes it) SNP i is dropped and the scan moves to the next i,
+ *                  otherwise SNP j is dropped.  Not claimed: byte parity with the plink binary, whose window refill and MAF epsilon
+ *                  differ in detail.  The device writes a bitmap of the pairs above the threshold (ceil((window - 1) / 32) words per
+ *                  SNP, in slabs of at most 256 MiB; FPCA_ENOMEM with the sizes in the message when a slab does not fit), the rule runs
+ *                  on the host.
+ *   Both: FPCA_EINVAL for a NULL argument, span == 0, window < 2, step < 1, step > window, r2 NaN or outside [0, 1], a range outside the
+ *   context, N > 2^25 (the integers above stay below 2^53), a dense context, a context under a sample mask or with a preloaded mean/sd
+ *   (the statistic is over all N samples), and one shard of several.  The context is not changed. */
+int fpca_ld_band(fpca_ctx *ctx, uint64_t snp0, uint64_t nsnp, uint32_t span, double *r2 /* [nsnp][span] */);
+int fpca_ld_prune(fpca_ctx *ctx, const uint32_t *chrom /* [P_g] or NULL */, uint32_t window, uint32_t step, double r2,
+                  uint8_t *keep /* in/out, like fpca_snp_qc */, uint64_t *n_kept);
+
 /* ------------------------------------------------------------------------------------------------
  * Operator.  b columns at a time; b = 1 is exactly the reference's perform_op.
  *   fpca_apply_xxt : Y = X_g X_g' B        replaces SVDWideOnline::perform_op / perform_op_mat

@@ -105,6 +105,17 @@ int fpca_debug_snp_qc_rule(const double *mean, const uint32_t *n_missing, uint64
  * allocated before the clock starts; one untimed launch, then `reps` timed ones on src's stream.  Milliseconds per launch and the bytes
  * one launch moves (2 pitch P_kept: read and written).  src is not changed. */
 int fpca_debug_snp_subset_bench(fpca_ctx *src, const uint8_t *keep, int reps, double *ms_per_launch, double *bytes_per_launch);
+/* diagnostic (tests): the pruning rule of fpca_ld_prune on caller arrays, no context and no device involved.  bits: the band bitmap,
+ * P rows of ceil((window - 1) / 32) uint32 words, bit d - 1 of row i set when r2(i, i + d) is above the threshold (bits of pairs past
+ * the last SNP or across a chromosome boundary are ignored); totals: uint64 [P][3] = calls, sum x, sum x^2 over the SNP's own calls;
+ * maf[P]; chrom[P] or NULL; keep[P] in and out.  FPCA_EINVAL for the window / step fpca_ld_prune refuses. */
+int fpca_debug_ld_prune_rule(const uint32_t *bits, uint64_t P, uint32_t window, uint32_t step, const uint64_t *totals, const double *maf,
+                             const uint32_t *chrom, uint8_t *keep, uint64_t *n_kept);
+/* time the bitmap kernel of fpca_ld_prune alone (scripts/ld_prune_measure.py) over all SNPs of the context at threshold r2 = 0.05:
+ * per-SNP totals and the bitmap are ready before the clock starts; one untimed launch, then `reps` launches with a pair of HIP events
+ * around each, ms[reps].  *macs (may be NULL): int8 multiply-accumulates one launch issues (32 x 32 x 32 per MFMA, pad samples and
+ * pad SNPs included). */
+int fpca_bench_ld(fpca_ctx *ctx, uint32_t span, int reps, double *ms, double *macs);
 
 #ifdef __cplusplus
 }
