@@ -124,6 +124,9 @@ SIGNATURES = {
     "fpca_create_snp_subset": (_I, [C.POINTER(_P), _P, _P, _I]),
     "fpca_ld_band": (_I, [_P, _U64, _U64, C.c_uint32, _P]),
     "fpca_ld_prune": (_I, [_P, _P, C.c_uint32, C.c_uint32, _D, _P, C.POINTER(_U64)]),
+    "fpca_king_block": (_I, [_P, _U64, _U64, _U64, _U64, _P]),
+    "fpca_king_pairs": (_I, [_P, _P, _D, _U64, _P, _P, _P, C.POINTER(_U64)]),
+    "fpca_king_cutoff": (_I, [_P, _D, _P, C.POINTER(_U64)]),
     "fpca_apply_xxt": (_I, [_P, _P, C.c_int64, _I, _P, C.c_int64]),
     "fpca_apply_xt": (_I, [_P, _P, C.c_int64, _I, _P, C.c_int64]),
     "fpca_apply_x": (_I, [_P, _P, C.c_int64, _I, _P, C.c_int64]),
@@ -169,6 +172,8 @@ SIGNATURES = {
     "fpca_debug_snp_subset_bench": (_I, [_P, _P, _I, C.POINTER(_D), C.POINTER(_D)]),
     "fpca_debug_ld_prune_rule": (_I, [_P, _U64, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.POINTER(_U64)]),
     "fpca_bench_ld": (_I, [_P, C.c_uint32, _I, _P, C.POINTER(_D)]),
+    "fpca_debug_king_rule": (_I, [_P, _P, _U64, _U64, _P, C.POINTER(_U64)]),
+    "fpca_bench_king": (_I, [_P, _I, _P, C.POINTER(_D)]),
 }
 
 ABI_VERSION = 4  # FPCA_ABI_VERSION of the include/fpca.h the structures above mirror

@@ -235,6 +235,62 @@ class Context:
         check(lib().fpca_bench_ld(self.h, int(span), int(reps), _p(ms), C.byref(macs)))
         return ms, macs.value
 
+    # ---- kinship ------------------------------------------------------------------------------------
+    def _sample_keep(self, keep):
+        if keep is None:
+            return None
+        keep = np.asarray(keep)
+        if keep.shape != (self.N,):
+            raise ValueError("keep must have one entry per sample (%d), it has shape %s" % (self.N, keep.shape))
+        return np.ascontiguousarray(keep != 0, dtype=np.uint8)
+
+    def king_block(self, i0, ni, j0, nj):
+        """fpca_king_block: the ni x nj array of KING-robust kinship between sample i0 + a and sample j0 + b, any rectangle (at i == j the
+        formula gives 0.5, or NaN for a sample without a heterozygous call); NaN where the pair shares no heterozygous call of the less
+        heterozygous sample."""
+        i0, ni, j0, nj = int(i0), int(ni), int(j0), int(nj)
+        if min(i0, ni, j0, nj) < 0:
+            raise ValueError("i0, ni, j0 and nj are non-negative")
+        out = np.empty((max(ni, 1), max(nj, 1)), dtype=np.float64)  # (a zero-sized request still reaches the library's refusal)
+        check(lib().fpca_king_block(self.h, i0, ni, j0, nj, _p(out)))
+        return out[:ni, :nj]
+
+    def king_pairs(self, thr, keep=None, max_pairs=1 << 24):
+        """fpca_king_pairs: (i, j, phi) of every pair of samples i < j with kinship phi > thr, sorted by (i, j), among the samples of `keep`
+        (a boolean array with one entry per sample; None: all).  FpcaError (code -4, the message names the count) when more than max_pairs
+        qualify."""
+        k8 = self._sample_keep(keep)
+        max_pairs = int(max_pairs)
+        if max_pairs < 0:
+            raise ValueError("max_pairs is non-negative")
+        room = max(min(max_pairs, self.N * (self.N - 1) // 2), 1)
+        i = np.empty(room, dtype=np.uint32)
+        j = np.empty(room, dtype=np.uint32)
+        phi = np.empty(room, dtype=np.float64)
+        n = C.c_uint64(0)
+        check(lib().fpca_king_pairs(self.h, _p(k8), float(thr), max_pairs, _p(i), _p(j), _p(phi), C.byref(n)))
+        return i[:n.value].copy(), j[:n.value].copy(), phi[:n.value].copy()
+
+    def king_cutoff(self, thr=0.0884, keep=None):
+        """fpca_king_cutoff: the boolean mask of the samples left after removing, among those of `keep` (None: all), one sample at a time
+        -- the one in most pairs with kinship above thr, the largest index among equals -- until no such pair remains.  0.0884 separates
+        second-degree relatives from third-degree ones (0.177: first from second, 0.354: duplicates)."""
+        k8 = self._sample_keep(keep)
+        if k8 is None:
+            k8 = np.ones(self.N, dtype=np.uint8)
+        n = C.c_uint64(0)
+        check(lib().fpca_king_cutoff(self.h, float(thr), _p(k8), C.byref(n)))
+        out = k8 != 0
+        assert int(out.sum()) == n.value
+        return out
+
+    def bench_king(self, reps=5):
+        """fpca_bench_king: (milliseconds of each of `reps` passes of the pair kernel over the whole triangle, int8 MACs one pass issues)."""
+        ms = np.zeros(int(reps), dtype=np.float64)
+        macs = C.c_double(0)
+        check(lib().fpca_bench_king(self.h, int(reps), _p(ms), C.byref(macs)))
+        return ms, macs.value
+
     def set_total_snps(self, P_total):
         check(lib().fpca_set_total_snps(self.h, int(P_total)))
         self.P_total = int(P_total)
@@ -489,7 +545,8 @@ class Context:
 
 
 def flashpca(X, ndim=10, stand="binom2", divisor="p", maxiter=500, tol=1e-6, do_loadings=False, return_scale=True,
-             device=0, verbose=False, accum="auto", keep=None, snps=None, maf=0.0, geno=1.0, ld=None, **solver_kw):
+             device=0, verbose=False, accum="auto", keep=None, snps=None, maf=0.0, geno=1.0, ld=None, unrelated=None,
+             **solver_kw):
     """PCA of a PLINK fileset; mirrors flashpca() of the reference's R package for the PLINK-prefix input
     (flashpcaR/R/flashpca.R:99-204 -> flashpca_plink_internal, flashpcaR/src/flashpca.cpp:96-197).
 
@@ -504,6 +561,10 @@ def flashpca(X, ndim=10, stand="binom2", divisor="p", maxiter=500, tol=1e-6, do_
     scale have one row per kept SNP, divisor "p" is the kept count, and the result gains `snps_kept`, the mask over the .bim rows.
     ld: (window, step, r2) -- LD pruning in the style of PLINK's --indep-pairwise, windows and steps in SNPs, chromosomes from the .bim,
     applied to the survivors of snps / maf / geno (Context.ld_prune); r2 is over all samples, so not together with keep=.
+    unrelated: a kinship threshold (0.0884: no pair closer than third degree).  PLINK input only.  After snps / maf / geno / ld -- which
+    stay over all samples, the usual QC-then-KING order, and are allowed with it as long as keep is None -- Context.king_cutoff on the
+    selected SNPs picks the samples (among those of keep=, if given), and the PCA runs on them as under keep=: the result gains
+    `unrelated_kept`, the mask over the samples, and `projection_all`.
     Returns values, vectors, projection, loadings, center, scale, pve.
     """
     if divisor not in DIVISOR:
@@ -520,6 +581,10 @@ def flashpca(X, ndim=10, stand="binom2", divisor="p", maxiter=500, tol=1e-6, do_
             raise ValueError("ld prunes the SNPs of a PLINK fileset; it does not apply to a numeric matrix")
         if keep is not None:
             raise ValueError("ld cannot be combined with keep: PLINK takes r2 over the kept samples, r2 here is over all samples")
+    if unrelated is not None:
+        unrelated = float(unrelated)
+        if not isinstance(X, str):
+            raise ValueError("unrelated selects samples by the kinship of a PLINK fileset's genotypes; it does not apply to a numeric matrix")
     if isinstance(X, str):
         if stand not in STANDARDISE:
             raise ValueError("stand must be one of %s" % sorted(STANDARDISE))  # R: match.arg
@@ -539,12 +604,18 @@ def flashpca(X, ndim=10, stand="binom2", divisor="p", maxiter=500, tol=1e-6, do_
             if keep.shape != (ctx.N,):
                 raise ValueError("keep must have one entry per sample (%d), it has shape %s" % (ctx.N, keep.shape))
             keep = keep != 0
+        unrelated_kept = None
+        if unrelated is not None:
+            keep = unrelated_kept = ctx.king_cutoff(unrelated, keep=keep)
+        if keep is not None:
             ctx.set_sample_mask(keep)
         r = ctx.pca(ndim=ndim, tol=tol, maxiter=maxiter, div=divisor, do_loadings=do_loadings, verbose=int(verbose),
                     **solver_kw)
     res = dict(values=r["d"], vectors=r["U"], projection=r["Px"], loadings=r["V"], pve=r["pve"], info=r["info"])
     if keep is not None:
         res.update(vectors=r["U"][keep], projection=r["Px"][keep], projection_all=r["Px"])
+    if unrelated_kept is not None:
+        res["unrelated_kept"] = unrelated_kept
     if snps_kept is not None:
         res["snps_kept"] = snps_kept
     if return_scale:
@@ -976,6 +1047,22 @@ def ld_prune(prefix, window=1000, step=50, r2=0.05, snps=None, maf=0.0, geno=1.0
     N = count_fam_rows(prefix + ".fam")
     with Context.from_bed(prefix + ".bed", N, device=device, accum="fp64") as full:
         return _selection_mask(full, prefix, snps, qc, maf, geno, ld)
+
+
+def king_cutoff(prefix, thr=0.0884, snps=None, maf=0.0, geno=1.0, ld=None, keep=None, device=0):
+    """The unrelated samples of a PLINK fileset, picked on the GPU in the manner of `plink2 --king-cutoff thr`: a boolean mask over the
+    rows of prefix.fam in which no pair has KING-robust kinship above thr (Context.king_cutoff).  snps / maf / geno / ld as in flashpca():
+    they are applied first, over all samples, and the kinship is that of the selected SNPs.  keep: a boolean array with one entry per
+    sample; the cutoff runs among those.  Not byte-compatible with plink2 or KING (the order in which samples go differs)."""
+    qc = not (maf <= 0 and geno >= 1)
+    if ld is not None:
+        ld = _ld_args(ld)
+    N = count_fam_rows(prefix + ".fam")
+    with Context.from_bed(prefix + ".bed", N, device=device, accum="fp64") as full:
+        if snps is None and not qc and ld is None:
+            return full.king_cutoff(thr, keep=keep)
+        with _select_snps(full, prefix, snps, qc, maf, geno, ld)[0] as sub:
+            return sub.king_cutoff(thr, keep=keep)
 
 
 def project(X, loadings, orig_mean=None, orig_sd=None, ref_alleles=None, divisor="p", device=0, check_bim=True):

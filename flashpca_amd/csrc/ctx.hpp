@@ -17,6 +17,8 @@
 //                       the kept SNPs into a new context
 //   ld_band.hip         fpca_ld_band / fpca_ld_prune: windowed pairwise r2 as a banded integer Gram of the packed matrix with itself
 //                       (k_ld_band, six exact int8 products per pair), the --indep-pairwise rule on the host
+//   king.hip            fpca_king_block / fpca_king_pairs / fpca_king_cutoff: KING-robust kinship as the same Gram on a sample-major copy
+//                       (k_king, five products per pair; the loop itself is ld_planes.hpp), the greedy unrelated-sample rule on the host
 // MI355X / gfx950 only; there is no CPU fallback anywhere in the library.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -323,6 +325,12 @@ void snp_qc_check_thresholds(const char *fn, double min_maf, double max_missing)
 uint64_t ld_prune_rule(const uint32_t *bits, uint32_t words, uint64_t P, uint32_t window, uint32_t step, const uint64_t *totals,
                        const double *maf, const uint32_t *chrom, uint8_t *keep);
 void ld_check_window(const char *fn, uint32_t window, uint32_t step); // FPCA_EINVAL: window < 2, step < 1, step > window
+
+// ---- king.hip ---------------------------------------------------------------------------------------------
+// host only: the rule of fpca_king_cutoff (include/fpca.h).  Graph on the samples with keep != 0, an edge per listed pair (i[k], j[k]), k <
+// n_pairs, all below N; while an edge remains the sample of largest current degree goes, the largest index among equals.  keep[N] in and
+// out (entries become 0 / 1, a 0 stays 0); returns the number left non-zero.
+uint64_t king_cutoff_rule(const uint32_t *i, const uint32_t *j, uint64_t n_pairs, uint64_t N, uint8_t *keep);
 
 // ---- download.hip -----------------------------------------------------------------------------------------
 // d_img: device, column-major N x ncols with leading dimension N -> host (ld) and, scaled per column, host2 (ld2); synchronises

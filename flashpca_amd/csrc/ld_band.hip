@@ -23,13 +23,11 @@
 #include <cmath>
 
 #include "ctx.hpp"
+#include "ld_planes.hpp"
 
 using namespace fpca;
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
 
 constexpr int LD_TILE = 64;                        // records per workgroup tile side (2 waves x 32)
 constexpr uint64_t LD_MAX_N = 1ull << 25;          // 4 N^2 < 2^53: every integer of the statistic is exact in a double
@@ -65,66 +63,6 @@ __global__ __launch_bounds__(256) void k_ld_totals(const uint8_t *__restrict__ p
    if (lane == 0) reinterpret_cast<uint4 *>(tot)[rec] = make_uint4(2 * c2 + c1, 4 * c2 + c1, ce, 0u);
 }
 
-// byte[code] of the three planes, 16 codes of one dword -> 16 bytes each, in the order of i8_decode (codes q, q + 4, q + 8, q + 12 in
-// the four bytes of dword q; both operands are decoded alike, so the order within the 32-k step does not matter)
-template <bool GENERAL>
-__device__ __forceinline__ void ld_decode(uint32_t w, v4i &x, v4i &q, v4i &e)
-{
-#pragma unroll
-   for (int s = 0; s < 4; s++) {
-      const uint32_t sel = (w >> (2 * s)) & 0x03030303u;
-      x[s] = (int)__builtin_amdgcn_perm(0u, 0x00010002u, sel);
-      if (GENERAL) {
-         q[s] = (int)__builtin_amdgcn_perm(0u, 0x00010004u, sel);
-         e[s] = (int)__builtin_amdgcn_perm(0u, 0x00000100u, sel);
-      }
-   }
-}
-
-template <bool GENERAL>
-__device__ __forceinline__ void ld_products(const uint4 *__restrict__ pa, const uint4 *__restrict__ pb, uint32_t nchunks, v16i (&acc)[6])
-{
-   uint4 a[4], b[4];
-#pragma unroll
-   for (int p = 0; p < 4; p++) {
-      a[p] = pa[p];
-      b[p] = pb[p];
-   }
-   for (uint32_t c = 0; c < nchunks; c++) {
-      // the next chunk's 128 bytes per lane are in flight under this chunk's MFMAs (the last iteration re-reads its own chunk)
-      const uint32_t cn = c + 1 < nchunks ? c + 1 : c;
-      uint4 an[4], bn[4];
-#pragma unroll
-      for (int p = 0; p < 4; p++) {
-         an[p] = pa[(size_t)cn * 8 + p];
-         bn[p] = pb[(size_t)cn * 8 + p];
-      }
-#pragma unroll
-      for (int p = 0; p < 4; p++) {
-         const uint32_t wa[4] = {a[p].x, a[p].y, a[p].z, a[p].w}, wb[4] = {b[p].x, b[p].y, b[p].z, b[p].w};
-#pragma unroll
-         for (int d = 0; d < 4; d++) {
-            v4i xa, qa, ea, xb, qb, eb;
-            ld_decode<GENERAL>(wa[d], xa, qa, ea);
-            ld_decode<GENERAL>(wb[d], xb, qb, eb);
-            acc[0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(xa, xb, acc[0], 0, 0, 0);
-            if (GENERAL) {
-               acc[1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(xa, eb, acc[1], 0, 0, 0);
-               acc[2] = __builtin_amdgcn_mfma_i32_32x32x32_i8(ea, xb, acc[2], 0, 0, 0);
-               acc[3] = __builtin_amdgcn_mfma_i32_32x32x32_i8(qa, eb, acc[3], 0, 0, 0);
-               acc[4] = __builtin_amdgcn_mfma_i32_32x32x32_i8(ea, qb, acc[4], 0, 0, 0);
-               acc[5] = __builtin_amdgcn_mfma_i32_32x32x32_i8(ea, eb, acc[5], 0, 0, 0);
-            }
-         }
-      }
-#pragma unroll
-      for (int p = 0; p < 4; p++) {
-         a[p] = an[p];
-         b[p] = bn[p];
-      }
-   }
-}
-
 // tiles are counted from i0: tile t holds records [i0 + 64 t, i0 + 64 t + 64); workgroup w -> (tI, tJ) = (w / nj, w / nj + w % nj)
 template <bool BAND>
 __global__ __launch_bounds__(256, 2) void k_ld_band(const uint8_t *__restrict__ packed, size_t pitch, const uint32_t *__restrict__ tot, uint32_t npad,
@@ -150,9 +88,9 @@ __global__ __launch_bounds__(256, 2) void k_ld_band(const uint8_t *__restrict__ 
 #pragma unroll
       for (int r = 0; r < 16; r++) acc[m][r] = 0;
    if (general) {
-      ld_products<true>(pa, pb, nchunks, acc);
+      ld_products<true, true>(pa, pb, nchunks, acc);
    } else {
-      ld_products<false>(pa, pb, nchunks, acc);
+      ld_products<false, true>(pa, pb, nchunks, acc);
 #pragma unroll
       for (int r = 0; r < 16; r++) acc[5][r] = (int)npad; // e.e: the pad samples of both records; x.e = e.x = q.e = e.q = 0 stay
    }

@@ -230,6 +230,33 @@ int fpca_ld_band(fpca_ctx *ctx, uint64_t snp0, uint64_t nsnp, uint32_t span, dou
 int fpca_ld_prune(fpca_ctx *ctx, const uint32_t *chrom /* [P_g] or NULL */, uint32_t window, uint32_t step, double r2,
                   uint8_t *keep /* in/out, like fpca_snp_qc */, uint64_t *n_kept);
 
+/* Kinship: the KING-robust estimator (Manichaikul et al. 2010) between the samples of the resident matrix, on the int8 matrix cores, and
+ * an unrelated-sample cutoff on top of it.  The mask it leaves feeds fpca_set_sample_mask.
+ *   The statistic, for samples i and j, dosage x in {0,1,2}, q = x^2, h = 2x - q (1 at a heterozygous call), over the SNPs of the context
+ *   called in BOTH samples:
+ *      het_i = sum h_i, het_j = sum h_j, D = sum (x_i - x_j)^2, hmin = min(het_i, het_j)                   (exact integers)
+ *      phi = (double)(2 hmin - D) / (double)(4 hmin)         (= 1/2 - D / (4 hmin); int64 numerator and denominator, ONE fp64 divide)
+ *   phi is NaN when hmin == 0 (tested, not left to the divide); a NaN is never above a threshold; all comparisons are strict (phi > thr).
+ *   A duplicate without a missing call gives exactly 0.5.
+ *   fpca_king_block   phi[ni][nj], row-major: phi[a][b] is the statistic of samples i0 + a and j0 + b, for any rectangle (j <= i included;
+ *                     at i == j the formula gives 0.5 or NaN).  FPCA_EINVAL when the buffer would exceed 1 GiB.
+ *   fpca_king_pairs   every pair i < j with phi > thr whose samples both have keep != 0 (keep: N bytes, or NULL for all), sorted by (i, j),
+ *                     in i[], j[], phi[] (max_pairs entries each); *n_pairs = their number.  When more than max_pairs qualify the call
+ *                     returns FPCA_ENOMEM, *n_pairs is the number needed and the message names it; the arrays are then not written.
+ *   fpca_king_cutoff  keep[N] in and out, as for fpca_snp_qc: an entry that is 0 stays 0; *n_kept (may be NULL) = entries left non-zero.
+ *                     The pair pass above (room for 2^26 pairs, else FPCA_ENOMEM), then on the host: a graph on the samples with keep != 0
+ *                     with an edge for every listed pair; while an edge remains, the sample of largest current degree is dropped, the one
+ *                     of largest index among equals.  The purpose of plink2 --king-cutoff; byte parity with plink2 or KING is not claimed.
+ *   Every call makes its own sample-major copy of the packed matrix (as large as the matrix; FPCA_ENOMEM with both sizes in the message
+ *   when it does not fit) and frees it before it returns.
+ *   All: FPCA_EINVAL, before any device work, for a NULL argument, a range outside the context, a NaN thr, a dense context, a context under
+ *   a sample mask (pass the mask as keep instead), one shard of several, and more than 2^28 SNPs (the sums stay below 2^31).  A preloaded
+ *   mean/sd is not refused: nothing here reads it.  The context is not changed. */
+int fpca_king_block(fpca_ctx *ctx, uint64_t i0, uint64_t ni, uint64_t j0, uint64_t nj, double *phi /* [ni][nj] */);
+int fpca_king_pairs(fpca_ctx *ctx, const uint8_t *keep /* [N] or NULL */, double thr, uint64_t max_pairs, uint32_t *i, uint32_t *j, double *phi,
+                    uint64_t *n_pairs);
+int fpca_king_cutoff(fpca_ctx *ctx, double thr, uint8_t *keep /* [N] in/out, like fpca_snp_qc */, uint64_t *n_kept);
+
 /* ------------------------------------------------------------------------------------------------
  * Operator.  b columns at a time; b = 1 is exactly the reference's perform_op.
  *   fpca_apply_xxt : Y = X_g X_g' B        replaces SVDWideOnline::perform_op / perform_op_mat

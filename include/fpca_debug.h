@@ -116,6 +116,14 @@ int fpca_debug_ld_prune_rule(const uint32_t *bits, uint64_t P, uint32_t window, 
  * around each, ms[reps].  *macs (may be NULL): int8 multiply-accumulates one launch issues (32 x 32 x 32 per MFMA, pad samples and
  * pad SNPs included). */
 int fpca_bench_ld(fpca_ctx *ctx, uint32_t span, int reps, double *ms, double *macs);
+/* diagnostic (tests): the rule of fpca_king_cutoff on caller arrays, no context and no device involved.  (i[k], j[k]), k < n_pairs: the
+ * pairs above the threshold, in any order, samples below N; keep[N] in and out.  FPCA_EINVAL for a pair outside the N samples. */
+int fpca_debug_king_rule(const uint32_t *i, const uint32_t *j, uint64_t n_pairs, uint64_t N, uint8_t *keep, uint64_t *n_kept);
+/* time the pair kernel of fpca_king_pairs alone (scripts/king_measure.py) over the whole triangle at thr = 0.0884, no keep: the
+ * sample-major copy and the per-sample totals are ready before the clock starts; one untimed pass, then `reps` passes (every launch of the
+ * triangle) with a pair of HIP events around each, ms[reps].  *macs (may be NULL): int8 multiply-accumulates one pass issues (32 x 32 x
+ * 32 per MFMA, pad SNPs included). */
+int fpca_bench_king(fpca_ctx *ctx, int reps, double *ms, double *macs);
 
 #ifdef __cplusplus
 }
