@@ -166,7 +166,9 @@ SIGNATURES = {
     "fpca_debug_k4_inplace": (_I, [_P, _I, _I, _P, _P, _P, _I, _P, _P]),
     "fpca_debug_fp_plan": (_I, [_P, _I, C.POINTER(_I)]),
     "fpca_debug_poison_partials": (_I, [_P]),
-    "fpca_debug_f_sf": (_I, [_D, _U64, _I, C.POINTER(_D), C.POINTER(_D)]),
+    "fpca_debug_missing_lists": (_I, [_P, _I, _I, _P, _P, _U64, C.POINTER(_U64)]),
+    "fpca_debug_gather": (_I, [_I, _I, _P, _P, _U64, _P, _U64, _P, _P, _P, _U64, _U64, _I, _D, _P, C.POINTER(_I)]),
+    "fpca_debug_f_sf":(_I, [_D, _U64, _I, C.POINTER(_D), C.POINTER(_D)]),
     "fpca_debug_fold_stats": (_I, [_P, _P, _I, _P, _I, _P]),
     "fpca_debug_snp_qc_rule": (_I, [_P, _P, _U64, _U64, _D, _D, _P, C.POINTER(_U64)]),
     "fpca_debug_snp_subset_bench": (_I, [_P, _P, _I, C.POINTER(_D), C.POINTER(_D)]),

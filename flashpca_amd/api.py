@@ -510,6 +510,16 @@ class Context:
         check(lib().fpca_debug_fold_stats(self.h, _p(folds8), int(nfolds), _p(counts), -1 if which_fold is None else int(which_fold), _p(ms)))
         return counts, ms
 
+    def missing_lists(self, b, by_sample):
+        """fpca_debug_missing_lists: (ptr, idx) of the missing-call index lists of a list route (missing_mode(b) 3 or 4), by SNP
+        (by_sample False: P + 1 pointers, sample indices) or by sample (N + 1 pointers, SNP indices); FpcaError on any other route."""
+        ptr = np.zeros((self.N if by_sample else self.P) + 1, dtype=np.uint32)
+        nnz = C.c_uint64(0)
+        check(lib().fpca_debug_missing_lists(self.h, int(b), int(bool(by_sample)), _p(ptr), None, 0, C.byref(nnz)))
+        idx = np.zeros(max(nnz.value, 1), dtype=np.uint32)
+        check(lib().fpca_debug_missing_lists(self.h, int(b), int(bool(by_sample)), _p(ptr), _p(idx), idx.size, C.byref(nnz)))
+        return ptr, idx[:nnz.value]
+
     # ---- measurement -----------------------------------------------------------------------------------
     def bench_apply(self, b=32, steps=10, warmup=2):
         r = BenchResult()
@@ -542,6 +552,32 @@ class Context:
         ms, by = C.c_double(0), C.c_double(0)
         check(lib().fpca_bench_stats(self.h, reps, C.byref(ms), C.byref(by)))
         return ms.value, by.value
+
+
+def debug_gather(ptr, idx, V, b, rows_out=None, rowscale=None, colw=None, init=None, short_lists=False, avg_len=0.0):
+    """fpca_debug_gather: the gather-sum kernels of the missing-call list routes on caller data.  ptr (nrec + 1), idx: the lists; V:
+    v_rows x b, fp64 or fp32 (fp32 takes colw, b factors; fp64 may take rowscale, v_rows factors); init: rows_out x b or None.
+    Returns (out, rows_out x b fp64; the kernel that ran: 1, 2 or 3)."""
+    ptr = np.ascontiguousarray(ptr, dtype=np.uint32)
+    idx = np.ascontiguousarray(idx, dtype=np.uint32)
+    f32 = np.asarray(V).dtype == np.float32
+    V = np.ascontiguousarray(V, dtype=np.float32 if f32 else np.float64)
+    nrec = ptr.size - 1
+    rows_out = nrec if rows_out is None else int(rows_out)
+    if V.ndim != 2 or V.shape[1] != b or nrec < 0 or int(ptr[-1]) != idx.size:
+        raise ValueError("V is v_rows x b, ptr has one entry more than there are lists and ends at len(idx)")
+    rowscale = None if rowscale is None else np.ascontiguousarray(rowscale, dtype=np.float64)
+    colw = None if colw is None else np.ascontiguousarray(colw, dtype=np.float64)
+    init = None if init is None else np.ascontiguousarray(init, dtype=np.float64)
+    if (rowscale is not None and rowscale.shape != (V.shape[0],)) or (colw is not None and colw.shape != (b,)) or (
+            init is not None and init.shape != (rows_out, b)):
+        raise ValueError("rowscale has one entry per row of V, colw one per column, init is rows_out x b")
+    out = np.empty((max(rows_out, 1), b), dtype=np.float64)
+    variant = C.c_int(0)
+    idx_arg = idx if idx.size else np.zeros(1, dtype=np.uint32)
+    check(lib().fpca_debug_gather(int(b), int(f32), _p(ptr), _p(idx_arg), idx.size, _p(V), V.shape[0], _p(rowscale), _p(colw), _p(init), nrec,
+                                  rows_out, int(bool(short_lists)), float(avg_len), _p(out), C.byref(variant)))
+    return out[:rows_out], variant.value
 
 
 def flashpca(X, ndim=10, stand="binom2", divisor="p", maxiter=500, tol=1e-6, do_loadings=False, return_scale=True,

@@ -468,6 +468,74 @@ int fpca_debug_poison_partials(fpca_ctx *ctx)
    });
 }
 
+// The index lists of the missing calls as the operator's list routes use them: built, if they are not there yet, by the call the
+// operator itself makes (sparse_or_dense for the route i8_mode returns), then downloaded.
+int fpca_debug_missing_lists(fpca_ctx *ctx, int b, int by_sample, uint32_t *ptr_out, uint32_t *idx_out, uint64_t idx_cap, uint64_t *nnz)
+{
+   return guarded([&] {
+      if (!ctx || !nnz || (b != 16 && b != 32 && b != 64)) throw Error(FPCA_EINVAL, "bad argument to fpca_debug_missing_lists");
+      HIP_CHECK(hipSetDevice(ctx->device));
+      ensure_stats(ctx);
+      if (!ctx->i8_S || !ensure_i8(ctx, b)) throw Error(FPCA_EINVAL, "fpca_debug_missing_lists: the context does not run the exact-integer arithmetic");
+      int mode = i8_mode(ctx, b);
+      if (mode == I8M_SPARSE || mode == I8M_HYBRID) mode = sparse_or_dense(ctx, b, mode);
+      if (mode != I8M_SPARSE && mode != I8M_HYBRID) throw Error(FPCA_EINVAL, "fpca_debug_missing_lists: the context is not on a route with index lists");
+      const uint32_t *d_ptr = by_sample ? ctx->d_smp_ptr : ctx->d_snp_ptr, *d_idx = by_sample ? ctx->d_smp_idx : ctx->d_snp_idx;
+      if (!d_ptr || !d_idx) throw Error(FPCA_EINVAL, "fpca_debug_missing_lists: the context holds no lists by sample");
+      const uint64_t nrec = by_sample ? ctx->N : ctx->P_g;
+      *nnz = ctx->hyb_view ? ctx->hyb_sparse_nnz : ctx->n_missing;
+      if (idx_out && idx_cap < *nnz) throw Error(FPCA_EINVAL, "fpca_debug_missing_lists: idx_out is too small (*nnz holds the length)");
+      HIP_CHECK(hipStreamSynchronize(ctx->stream));
+      if (ptr_out) HIP_CHECK(hipMemcpy(ptr_out, d_ptr, (nrec + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      if (idx_out && *nnz) HIP_CHECK(hipMemcpy(idx_out, d_idx, *nnz * sizeof(uint32_t), hipMemcpyDeviceToHost));
+   });
+}
+
+// kern::sparse_rows_sum / sparse_rows_sum_f32 on caller data, launched with the arguments the operator passes
+int fpca_debug_gather(int b, int use_f32, const uint32_t *ptr, const uint32_t *idx, uint64_t nnz, const void *V, uint64_t v_rows, const double *rowscale,
+                      const double *colw, const double *init, uint64_t nrec, uint64_t rows_out, int short_lists, double avg_len, double *out, int *variant)
+{
+   std::vector<void *> dev;
+   auto upload = [&](const void *h, size_t bytes) -> void * {
+      void *d = nullptr;
+      HIP_ALLOC(hipMalloc(&d, std::max<size_t>(bytes, 16)));
+      dev.push_back(d);
+      if (h && bytes) HIP_CHECK(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice));
+      return d;
+   };
+   const int rc = guarded([&] {
+      if ((b != 16 && b != 32 && b != 64) || !ptr || !idx || !V || !out || !variant || v_rows == 0 || v_rows >= (1ull << 32) || rows_out == 0 ||
+          nrec > rows_out || rows_out >= (1ull << 31) || nnz >= (1ull << 32))
+         throw Error(FPCA_EINVAL, "bad argument to fpca_debug_gather");
+      if (use_f32 ? (!colw || rowscale) : (colw != nullptr))
+         throw Error(FPCA_EINVAL, "fpca_debug_gather: fp32 rows take colw and no rowscale, fp64 rows no colw");
+      // every index the kernels will follow is checked here: they read ptr[0 .. nrec], idx[ptr[r] .. ptr[r + 1]) and the rows idx names
+      if (ptr[0] != 0 || ptr[nrec] != nnz) throw Error(FPCA_EINVAL, "fpca_debug_gather: ptr must run from 0 to nnz");
+      for (uint64_t r = 0; r < nrec; r++)
+         if (ptr[r + 1] < ptr[r]) throw Error(FPCA_EINVAL, "fpca_debug_gather: ptr must not decrease");
+      for (uint64_t t = 0; t < nnz; t++)
+         if (idx[t] >= v_rows) throw Error(FPCA_EINVAL, "fpca_debug_gather: an index is outside V");
+      const size_t esz = use_f32 ? sizeof(float) : sizeof(double), out_bytes = (size_t)rows_out * b * sizeof(double);
+      const uint32_t *d_ptr = static_cast<const uint32_t *>(upload(ptr, (nrec + 1) * sizeof(uint32_t)));
+      const uint32_t *d_idx = static_cast<const uint32_t *>(upload(idx, nnz * sizeof(uint32_t)));
+      const void *d_V = upload(V, (size_t)v_rows * b * esz);
+      const double *d_rs = rowscale ? static_cast<const double *>(upload(rowscale, v_rows * sizeof(double))) : nullptr;
+      const double *d_cw = colw ? static_cast<const double *>(upload(colw, b * sizeof(double))) : nullptr;
+      const double *d_init = init ? static_cast<const double *>(upload(init, out_bytes)) : nullptr;
+      double *d_out = static_cast<double *>(upload(nullptr, out_bytes));
+      HIP_CHECK(hipMemset(d_out, 0xFF, out_bytes)); // NaNs: a row the kernel does not write cannot pass for a zero
+      *variant = kern::sparse_rows_sum_variant(b, rowscale != nullptr, short_lists != 0, avg_len);
+      if (use_f32)
+         kern::sparse_rows_sum_f32(d_ptr, d_idx, static_cast<const float *>(d_V), d_cw, b, nrec, rows_out, d_out, nullptr, d_init, short_lists != 0, avg_len);
+      else
+         kern::sparse_rows_sum(d_ptr, d_idx, static_cast<const double *>(d_V), d_rs, b, nrec, rows_out, d_out, nullptr, d_init, short_lists != 0, avg_len);
+      HIP_CHECK(hipDeviceSynchronize());
+      HIP_CHECK(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));
+   });
+   for (void *d : dev) (void)hipFree(d);
+   return rc;
+}
+
 int fpca_debug_mfma_peak(int waves_per_simd, int iters, int pattern, double *tflops)
 {
    return guarded([&] {

@@ -258,6 +258,9 @@ constexpr int I8M_FULL = 0, I8M_SKIP = 1, I8M_NONE = 2, I8M_SPARSE = 3, I8M_HYBR
 // context has been switched to the fp64 kernels for good.
 bool ensure_i8(fpca_ctx *c, int b);
 int i8_mode(fpca_ctx *c, int b);
+// makes the missing-call index lists (and, for I8M_HYBRID, that route's buffers) of the list route `want` ready for width b; returns
+// the route to use: `want`, or what i8_mode gives once the lists have turned out not to fit
+int sparse_or_dense(fpca_ctx *c, int b, int want = I8M_SPARSE);
 void i8_zero_meta(fpca_ctx *c, hipStream_t s);
 // the operand of K2 already sliced elsewhere (row-sharded exchange): all rows' slices row-major, the column maxima / weights that go
 // with them, and an [N_pad][b] fp64 buffer the scaled operand may be written to for the sparse gathers of an exact pass

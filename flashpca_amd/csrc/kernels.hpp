@@ -176,6 +176,9 @@ void sparse_rows_sum(const uint32_t *ptr, const uint32_t *idx, const double *V, 
 // operand's slice weights, which carry the exponent back)
 void sparse_rows_sum_f32(const uint32_t *ptr, const uint32_t *idx, const float *V, const double *colw, int b, uint64_t nrec, uint64_t rows_out,
                          double *out, hipStream_t stream, const double *init = nullptr, bool short_lists = false, double avg_len = 0);
+// which kernel the two launches above take for these arguments (rowscale: a per-row factor is given): 1 one wave per row, 2 the same
+// with batched index reads, 3 several rows per wave
+int sparse_rows_sum_variant(int b, bool rowscale, bool short_lists, double avg_len);
 void i8_rowscales(const double *mean, const double *sd, uint64_t P_g, uint64_t P_pad, double *inv_sd, double *mu_inv_sd,
                   hipStream_t stream);
 void transpose_packed(const uint8_t *in, size_t pitch_in, uint64_t N_pad, uint64_t P_pad, uint8_t *out, size_t pitch_out,

@@ -1667,12 +1667,10 @@ __global__ __launch_bounds__(256) void k_sparse_rows_sum_short(const uint32_t *_
    }
 }
 
-template <class VT>
-static void sparse_rows_sum_t(const uint32_t *ptr, const uint32_t *idx, const VT *V, const double *rowscale, int b, uint64_t nrec,
-                              uint64_t rows_out, double *out, hipStream_t stream, const double *init, bool short_lists, const double *colw, double avg_len)
+// The gather kernel a launch takes: 1 = k_sparse_rows_sum, 2 = k_sparse_rows_sum_batched, 3 = k_sparse_rows_sum_short (which exists for
+// 16 and 32 columns and has no per-row factor: a request for it outside that is served by the batched kernel).
+int sparse_rows_sum_variant(int b, bool rowscale, bool short_lists, double avg_len)
 {
-   if (!rows_out) return;
-   const unsigned blocks = (unsigned)std::min<uint64_t>(65536, (rows_out + 3) / 4);
    // measured (scripts/ab_gather.sh, cfg3): the batched kernel takes 0.3 ms off the K3 gather (short lists per sample),
    // nothing off the K2 one and costs it 6-50 us at the small sizes -- so K3 takes the batched kernel, K2 the plain one.
    // Both sit at ~7 TB/s out of the Infinity Cache; with the gathered matrix resident in L2 the same kernel reaches 9.4 TB/s
@@ -1680,9 +1678,20 @@ static void sparse_rows_sum_t(const uint32_t *ptr, const uint32_t *idx, const VT
    static const int forced = FPCA_TEST_ENV("FPCA_GATHER") ? atoi(FPCA_TEST_ENV("FPCA_GATHER")) : 0; // 1 / 2 force one kernel (A/B)
    // 3: several rows per wave, for lists of a dozen entries (measured on the 1/8 shard of cfg3, 12.5 entries per sample: see DESIGN 3c)
    const int variant = forced ? forced : (avg_len > 0 && avg_len <= 24.0 && b <= 32 && !rowscale) ? 3 : ((rowscale || short_lists) ? 2 : 1);
+   if (variant == 3 && b <= 32 && !rowscale) return 3;
+   return variant == 1 ? 1 : 2;
+}
+
+template <class VT>
+static void sparse_rows_sum_t(const uint32_t *ptr, const uint32_t *idx, const VT *V, const double *rowscale, int b, uint64_t nrec,
+                              uint64_t rows_out, double *out, hipStream_t stream, const double *init, bool short_lists, const double *colw, double avg_len)
+{
+   if (!rows_out) return;
+   const unsigned blocks = (unsigned)std::min<uint64_t>(65536, (rows_out + 3) / 4);
+   const int variant = sparse_rows_sum_variant(b, rowscale != nullptr, short_lists, avg_len);
 #define FPCA_GATHER_CASE(B_)                                                                                                    \
    case B_:                                                                                                                     \
-      if (variant == 3 && B_ <= 32 && !rowscale) {                                                                              \
+      if (variant == 3 && B_ <= 32) {                                                                                           \
          const unsigned blocks3 = (unsigned)std::min<uint64_t>(65536, (rows_out + 4 * (64 / B_) - 1) / (4 * (64 / B_)));        \
          hipLaunchKernelGGL((k_sparse_rows_sum_short<(B_ <= 32 ? B_ : 32), VT>), dim3(blocks3), dim3(256), 0, stream, ptr, idx, V, nrec, rows_out, out, init, colw); \
       } else if (variant == 1)                                                                                                  \

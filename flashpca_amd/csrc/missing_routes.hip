@@ -475,7 +475,7 @@ void ensure_hybrid(fpca_ctx *c, int b)
 // The sparse route needs 8 bytes per missing call (2 GB at 500k x 100k and 0.5 %) plus one N x b plane.  If that does not
 // fit, the context takes the dense missing-indicator route (both integer matrices on the matrix cores) from here on --
 // out-of-memory only; any other failure is reported.  Returns the mode to use.
-int sparse_or_dense(fpca_ctx *c, int b, int want = I8M_SPARSE)
+int sparse_or_dense(fpca_ctx *c, int b, int want)
 {
    try {
       if (want == I8M_HYBRID && !c->hyb_view) { // (the shard qualified after the sample-major copy was made -- e.g. forced late)

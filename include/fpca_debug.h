@@ -88,6 +88,26 @@ int fpca_debug_fp_plan(fpca_ctx *ctx, int b, int out[6]);
  * stream: after one product has sized them, a plane or tile that the next product does not write shows in its result */
 int fpca_debug_poison_partials(fpca_ctx *ctx);
 
+/* diagnostic (tests/test_gpu_missing_gathers.py): the index lists of the missing calls that the exact-integer mode's list routes
+ * (fpca_missing_mode 3 and 4) gather over, for blocks of b columns (16, 32 or 64).  Makes the lists ready the way the operator does
+ * before its first product on such a route and downloads them; FPCA_EINVAL if the context is not on a list route for this b.
+ *   by_sample 0: one list per SNP, the samples with a missing call, ascending;  ptr_out: nsnps + 1 entries
+ *   by_sample 1: one list per sample, the SNPs with a missing call, ascending;  ptr_out: nsamples + 1 entries
+ * List r is idx_out[ptr_out[r] .. ptr_out[r + 1]).  *nnz: the length of idx; idx_out (may be NULL, as may ptr_out) is written if idx_cap
+ * >= *nnz, else FPCA_EINVAL with *nnz set.  On the hybrid route the lists are those of that route's view of the matrix: the SNPs whose
+ * indicator rows go to the matrix cores have empty lists and appear in no sample's list. */
+int fpca_debug_missing_lists(fpca_ctx *ctx, int b, int by_sample, uint32_t *ptr_out, uint32_t *idx_out, uint64_t idx_cap, uint64_t *nnz);
+/* diagnostic (tests/test_gpu_missing_gathers.py): the gather-sum kernels of those routes on caller data, host pointers, no context:
+ *   out[r][c] = (init ? init[r][c] : 0) + sum over t in [ptr[r], ptr[r + 1]) of V[idx[t]][c] (rowscale ? rowscale[idx[t]] : 1),  r < nrec,
+ * and init or 0 for nrec <= r < rows_out; row-major, b = 16, 32 or 64 columns.  ptr: nrec + 1 entries from 0 to nnz, not decreasing; idx:
+ * nnz entries below v_rows (checked before anything is launched).  use_f32 0: V is v_rows x b fp64, rowscale (may be NULL) v_rows
+ * factors, colw NULL.  use_f32 1: V is fp32 and the sums are multiplied by 32 colw[c], as for the rows the slicing pass leaves; no
+ * rowscale.  short_lists and avg_len go to the launch as the operator passes them (K2: 0, 0; K3: 1, listed calls per sample) and choose
+ * the kernel; *variant reports it: 1 one wave per row, 2 the same with batched index reads, 3 several rows per wave. */
+int fpca_debug_gather(int b, int use_f32, const uint32_t *ptr, const uint32_t *idx, uint64_t nnz, const void *V, uint64_t v_rows,
+                      const double *rowscale, const double *colw, const double *init, uint64_t nrec, uint64_t rows_out, int short_lists,
+                      double avg_len, double *out, int *variant);
+
 /* diagnostic (tests): the F tail of fpca_ucca, from the host build of the same source the finishing kernel runs (no device
  * involved): F = r2 / (1 - r2) (n - k - 1) / k and P = upper tail of F(k, n - k - 1) at F = I_{1 - r2}((n - k - 1) / 2, k / 2).
  * FPCA_EINVAL unless k >= 1 and n >= k + 2. */
