@@ -1,6 +1,9 @@
 // ctx.hpp -- PRIVATE to libfpca.so: the device context behind the opaque `fpca_ctx` of include/fpca.h, the error / HIP / RCCL
 // check macros, and the internal functions the translation units of the library share.  Nothing here is part of the ABI.
 //
+//   kernels.hip         K1 statistics, the fp64 / fp32 GEMMs, the dense path, K4 helpers, generator (declared in kernels.hpp, like the next two)
+//   kernels_i8.hip      exact-integer mode: slicing, the int8 GEMM and its combine, the packed layouts it reads
+//   missing_kernels.hip exact-integer mode: index lists of the missing calls, the gather-sums over them, the hybrid route's row shuffles
 //   cabi.cpp            extern "C" entry points of include/fpca.h (argument checks, error plumbing, fpca_pca / fpca_check)
 //   context.hip         context life cycle: allocation, .bed / synthetic / dense upload, K1 statistics, teardown
 //   missing_routes.hip  exact-integer mode: buffers, the choice of the missing-indicator route, the two sliced GEMM stages

@@ -25,6 +25,7 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "launch_check.hpp"
 #include "synth.hpp"
 
 namespace fpca {
@@ -35,12 +36,6 @@ typedef double d2 __attribute__((ext_vector_type(2)));   // 16-byte load/store u
 typedef uint32_t u4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u2 __attribute__((ext_vector_type(2)));
 #define FPCA_MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
-
-#define HIP_CHECK_LAUNCH()                                                                         \
-   do {                                                                                             \
-      hipError_t e__ = hipGetLastError();                                                           \
-      if (e__ != hipSuccess) throw Error(-3, std::string("kernel launch failed: ") + hipGetErrorString(e__)); \
-   } while (0)
 
 // ------------------------------------------------------------------------------------------------
 // padding fix-up: pad bits of the last valid byte -> "01" (missing)
@@ -58,7 +53,7 @@ void fix_last_byte(uint8_t *packed, size_t pitch, uint64_t np, int valid_in_last
    uint32_t keep = (1u << (2 * valid_in_last)) - 1u;
    unsigned grid = (unsigned)((P_g + 255) / 256);
    hipLaunchKernelGGL(k_fix_last_byte, dim3(grid), dim3(256), 0, stream, packed, pitch, np, keep, P_g);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -97,7 +92,7 @@ void repitch(const uint8_t *src, uint64_t np, uint64_t nrec, uint8_t *dst, size_
 {
    if (!nrec) return;
    hipLaunchKernelGGL(k_repitch, dim3((unsigned)nrec), dim3(256), 0, stream, src, np, dst, pitch);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -195,7 +190,7 @@ void bed_stats(const uint8_t *packed, size_t pitch, uint64_t N, uint64_t P_g, in
    if (P_g == 0) return;
    hipLaunchKernelGGL(k_bed_stats, dim3((unsigned)P_g), dim3(256), 0, stream, packed, pitch, N, stand_method, lut, mean,
                       sd, sumsq, nmiss);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 __global__ void k_lut_from_meansd(const double *mean, const double *sd, uint64_t P_g, double *lut)
@@ -211,7 +206,7 @@ void lut_from_meansd(const double *mean, const double *sd, uint64_t P_g, double 
 {
    if (P_g == 0) return;
    hipLaunchKernelGGL(k_lut_from_meansd, dim3((unsigned)((P_g + 255) / 256)), dim3(256), 0, stream, mean, sd, P_g, lut);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -596,7 +591,7 @@ static void launch_xt_b(const uint8_t *packed, size_t pitch, const double *lut, 
    dim3 grid((unsigned)(P_pad / (64 * MT)), (unsigned)nsplit);
    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_xt_b<RT, NT, MT, KC>), grid, dim3(256), smem, stream, packed, pitch, lut, B, Tpart, P_pad,
                       sc.total, sc.per_split);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 void xt_b(const uint8_t *packed, size_t pitch, const double *lut, const double *B, double *Tpart, uint64_t N_pad,
@@ -820,7 +815,7 @@ static void launch_x_t(const uint8_t *packed, size_t pitch, const double *lut, c
    dim3 grid((unsigned)(N_pad / (64 * MT)), (unsigned)nsplit);
    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_x_t<RT, MT, NT, KCX>), grid, dim3(256), smem, stream, packed, pitch, lut, T, Ypart,
                       N_pad, sc.total, sc.per_split);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 void x_t(const uint8_t *packed, size_t pitch, const double *lut, const double *T, double *Ypart, uint64_t N_pad,
@@ -916,7 +911,7 @@ void reduce_sum(const double *part, double *out, uint64_t count, int nsplit, hip
    if (nsplit >= 64 && count2 <= (1u << 16)) {
       hipLaunchKernelGGL(k_reduce_tall, dim3((unsigned)((count2 + 7) / 8)), dim3(256), 0, stream, reinterpret_cast<const d2 *>(part),
                          reinterpret_cast<d2 *>(out), count2, nsplit);
-      HIP_CHECK_LAUNCH();
+      launch_check();
       return;
    }
    uint64_t blocks = (count2 + 511) / 512;
@@ -924,7 +919,7 @@ void reduce_sum(const double *part, double *out, uint64_t count, int nsplit, hip
    if (blocks == 0) blocks = 1;
    hipLaunchKernelGGL(k_reduce_sum, dim3((unsigned)blocks), dim3(256), 0, stream, reinterpret_cast<const d2 *>(part),
                       reinterpret_cast<d2 *>(out), count2, nsplit);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1014,7 +1009,7 @@ void dense_standardise(double *Xd, uint64_t N_pad, uint64_t N, uint64_t P_g, int
 {
    if (P_g == 0) return;
    hipLaunchKernelGGL(k_dense_standardise, dim3((unsigned)P_g), dim3(256), 0, stream, Xd, N_pad, N, method, mean, sd, sumsq);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 // K2d: T[j][c] = sum_s Xd[j][s] B[s][c].  Workgroup = 128 columns-of-X (2 m-tiles per wave); lane (i, kq) streams
@@ -1193,7 +1188,7 @@ void xt_b_dense(const double *Xd, const double *B, double *Tpart, uint64_t N_pad
    case 64: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_xt_b_dense<4>), grid, dim3(256), smem, stream, Xd, N_pad, B, Tpart, P_pad, chunks_total, cps); break;
    default: throw Error(-1, "xt_b_dense: block width must be 16, 32, 48 or 64");
    }
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 void x_t_dense(const double *Xd, const double *T, double *Ypart, uint64_t N_pad, uint64_t P_pad, int b, int nsplit,
@@ -1210,7 +1205,7 @@ void x_t_dense(const double *Xd, const double *T, double *Ypart, uint64_t N_pad,
    case 64: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_x_t_dense<4>), grid, dim3(256), smem, stream, Xd, N_pad, T, Ypart, chunks_total, cps); break;
    default: throw Error(-1, "x_t_dense: block width must be 16, 32, 48 or 64");
    }
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1359,7 +1354,7 @@ void gram(const double *const *blocks, int nq, const double *W, double *part, ui
          hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gram_tiled<1, 8>), grid, dim3(256), 0, stream, blocks, W, part, N_pad, nq);
       else
          hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gram_tiled<2, 2>), grid, dim3(256), 0, stream, blocks, W, part, N_pad, nq);
-      HIP_CHECK_LAUNCH();
+      launch_check();
       return;
    }
    dim3 grid((unsigned)gram_splits(N_pad, rows), (unsigned)nq); // (`rows` only sets the number of workgroups: 4 partial planes each)
@@ -1368,7 +1363,7 @@ void gram(const double *const *blocks, int nq, const double *W, double *part, ui
    case 64: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gram<4>), grid, dim3(256), 0, stream, blocks, W, part, N_pad, rows, nq); break;
    default: throw Error(-1, "gram: block width must be 16, 32, 48 or 64");
    }
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1560,7 +1555,7 @@ void block_gemm(const double *const *blocks, int nq, const double *C, const doub
          else
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_block_gemm_lds<2, 3, TPW, false>), grid, dim3(256), 0, stream, blocks, nq, C, Init, Out, N_pad, nullptr);
       }
-      HIP_CHECK_LAUNCH();
+      launch_check();
       return;
    }
    dim3 grid((unsigned)(N_pad / 64));
@@ -1571,7 +1566,7 @@ void block_gemm(const double *const *blocks, int nq, const double *C, const doub
    case 64: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_block_gemm<4>), grid, dim3(256), 0, stream, blocks, nq, C, Init, Out, N_pad); break;
    default: throw Error(-1, "block_gemm: block width must be 16, 32, 48 or 64");
    }
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1697,7 +1692,7 @@ void update_gram(const double *const *blocks, int nq, const double *C, const dou
       hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_gram16<4>), dim3((unsigned)planes), dim3(256), 0, stream, blocks, nq, C, Init, Out, N_pad, tpw, gpart);
    else
       hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_gram16<7>), dim3((unsigned)planes), dim3(256), 0, stream, blocks, nq, C, Init, Out, N_pad, tpw, gpart);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1723,7 +1718,7 @@ void fill_random(double *blk, uint64_t N, uint64_t rows, int b, uint64_t seed, h
    uint64_t blocks = (total + 255) / 256;
    if (blocks > 8192) blocks = 8192;
    hipLaunchKernelGGL(k_fill_random, dim3((unsigned)blocks), dim3(256), 0, stream, blk, N, total, b, seed, row0);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 // *out_bits = max(*out_bits, bit pattern of max_i |a[i] - scale b[i]|) -- non-negative doubles order like their bit patterns
@@ -1744,7 +1739,7 @@ void max_abs_diff(const double *a, const double *b, double scale, uint64_t n, un
    if (!n) return;
    const unsigned blocks = (unsigned)std::min<uint64_t>(2048, (n + 255) / 256);
    hipLaunchKernelGGL(k_max_abs_diff, dim3(blocks), dim3(256), 0, stream, a, b, scale, n, out_bits);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 __global__ void k_block_to_colmajor(const double *blk, uint64_t N, int b, int ncols, double *out, uint64_t ld)
@@ -1763,7 +1758,7 @@ void block_to_colmajor(const double *blk, uint64_t N, int b, int ncols, double *
    if (blocks == 0) return;
    if (blocks > 8192) blocks = 8192;
    hipLaunchKernelGGL(k_block_to_colmajor, dim3((unsigned)blocks), dim3(256), 0, stream, blk, N, b, ncols, out, ld);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 __global__ void k_colmajor_to_block(const double *in, uint64_t ld, uint64_t N, uint64_t N_pad, int b, int ncols,
@@ -1783,7 +1778,7 @@ void colmajor_to_block(const double *in, uint64_t ld, uint64_t N, uint64_t N_pad
    uint64_t blocks = (N_pad * b + 255) / 256;
    if (blocks > 8192) blocks = 8192;
    hipLaunchKernelGGL(k_colmajor_to_block, dim3((unsigned)blocks), dim3(256), 0, stream, in, ld, N, N_pad, b, ncols, blk);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 __global__ void k_t_to_colmajor(const double *T, uint64_t P_g, int b, int ncols, const double *colscale, double *out,
@@ -1805,7 +1800,7 @@ void t_to_colmajor(const double *T, uint64_t P_g, int b, int ncols, const double
    if (blocks == 0) return;
    if (blocks > 8192) blocks = 8192;
    hipLaunchKernelGGL(k_t_to_colmajor, dim3((unsigned)blocks), dim3(256), 0, stream, T, P_g, b, ncols, colscale, out, ld);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 __global__ void k_colmajor_to_t(const double *in, uint64_t ld, uint64_t P_g, uint64_t P_pad, int b, int ncols, double *T)
@@ -1824,7 +1819,7 @@ void colmajor_to_t(const double *in, uint64_t ld, uint64_t P_g, uint64_t P_pad, 
    uint64_t blocks = (P_pad * b + 255) / 256;
    if (blocks > 8192) blocks = 8192;
    hipLaunchKernelGGL(k_colmajor_to_t, dim3((unsigned)blocks), dim3(256), 0, stream, in, ld, P_g, P_pad, b, ncols, T);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1880,7 +1875,7 @@ void synth_generate(uint8_t *packed, size_t pitch, uint64_t N, uint64_t snp_begi
    if (P_g == 0) return;
    hipLaunchKernelGGL(k_synth_generate, dim3((unsigned)P_g), dim3(256), 0, stream, packed, pitch, N, snp_begin, seed,
                       n_pop, fst_fp, miss_thr, maf_model, missing_model, conc_fp, med_q32, sig2_fp);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1896,7 +1891,7 @@ __global__ void k_mfma_layout_probe(const double *A /*16x4 row-major*/, const do
 void mfma_layout_probe(const double *A, const double *B, double *D, hipStream_t stream)
 {
    hipLaunchKernelGGL(k_mfma_layout_probe, dim3(1), dim3(64), 0, stream, A, B, D);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-// kernels.hpp -- launch wrappers of the hand-written gfx950 kernels (kernels.hip).
+// kernels.hpp -- launch wrappers of the hand-written gfx950 kernels; every section names the file that defines its wrappers.
 // All pointers are DEVICE pointers; every launch is asynchronous on `stream`.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -9,14 +9,17 @@
 namespace fpca {
 namespace kern {
 
-// rewrite the pad bits of the last valid byte of every record to the "missing" code (N % 4 != 0)
-// back-to-back records of np bytes -> rows of `pitch` bytes (upload path)
+// ---- upload path (kernels.hip) ----
+// back-to-back records of np bytes -> rows of `pitch` bytes
 void repitch(const uint8_t *src, uint64_t np, uint64_t nrec, uint8_t *dst, size_t pitch, hipStream_t stream);
+// rewrite the pad bits of the last valid byte of every record to the "missing" code (N % 4 != 0)
 void fix_last_byte(uint8_t *packed, size_t pitch, uint64_t np, int valid_in_last, uint64_t P_g, hipStream_t stream);
-// record gather (snp_subset.hip): dst[j][:] = src[idx[j]][:] over `pitch` bytes (a multiple of 16) for j < nrec; dst has the same pitch,
+// ---- record gather (snp_subset.hip) ----
+// dst[j][:] = src[idx[j]][:] over `pitch` bytes (a multiple of 16) for j < nrec; dst has the same pitch,
 // nothing at or after record nrec is written
 void gather_records(const uint8_t *src, size_t pitch, const uint32_t *idx, uint64_t nrec, uint8_t *dst, hipStream_t stream);
-// LD band (ld_band.hip).  ld_totals: tot[rec][4] = (sum x, sum x^2, codes "01" = missing calls + pad samples, 0) over the `pitch` bytes
+// ---- LD band (ld_band.hip) ----
+// ld_totals: tot[rec][4] = (sum x, sum x^2, codes "01" = missing calls + pad samples, 0) over the `pitch` bytes
 // of records [0, nrec).  ld_band: every pair i in [i0, i0 + ni), j in (i, min(i + span, jend - 1)] of records of `packed`; r2 != null:
 // r2[(i - i0) * span + (j - i - 1)] = the statistic (fp64); else bit (j - i - 1) of the row of `words` uint32 words of record i - i0 is
 // OR-ed into bits (zeroed by the caller) when the statistic is above thr.  npad = 4 pitch - N; jend <= records allocated.
@@ -24,6 +27,7 @@ void ld_totals(const uint8_t *packed, size_t pitch, uint64_t nrec, uint32_t *tot
 void ld_band(const uint8_t *packed, size_t pitch, const uint32_t *tot, uint32_t npad, uint64_t i0, uint64_t ni, uint64_t jend, uint32_t span,
              double *r2, uint32_t *bits, uint32_t words, double thr, bool force_general, hipStream_t stream);
 
+// ---- statistics, the fp64 / fp32 GEMMs, the dense path, K4 helpers, generator and probes (kernels.hip) ----
 // K1: per-SNP code counts -> mean, sd, lookup table (by raw PLINK code), sum of squares
 //   lut [P_pad][4], mean/sd/sumsq [P_pad]; rows >= P_g untouched (must be pre-zeroed)
 void bed_stats(const uint8_t *packed, size_t pitch, uint64_t N, uint64_t P_g, int stand_method, double *lut,
@@ -157,7 +161,17 @@ void gemm_i8(const uint8_t *packed, size_t pitch, const int8_t *Qg, const int8_t
              const SliceOp *next_ops, hipStream_t stream, hipEvent_t *gemm_events = nullptr, hipEvent_t before_combine = nullptr,
              bool e_only = false /* mode 2 only: multiply the missing-indicator matrix E instead of G.M; out = E Q */,
              bool tiled = false /* `packed` is in the band-tiled layout (two-matrix and G.M-alone kernels) */);
-// the hybrid missing-indicator route's row shuffles (kernels_i8.hip)
+void i8_rowscales(const double *mean, const double *sd, uint64_t P_g, uint64_t P_pad, double *inv_sd, double *mu_inv_sd,
+                  hipStream_t stream);
+void transpose_packed(const uint8_t *in, size_t pitch_in, uint64_t N_pad, uint64_t P_pad, uint8_t *out, size_t pitch_out,
+                      hipStream_t stream, bool tiled = false /* write the band-tiled layout */);
+// out = the band-tiled arrangement of the row-major records in[rows][pitch] (rows a multiple of 32, pitch of 64)
+void tile_packed(const uint8_t *in, size_t pitch, uint64_t rows, uint8_t *out, hipStream_t stream);
+double mfma_i8_peak_tops(int waves_per_simd, int iters, uint32_t fill, hipStream_t stream);
+void mfma_i8_probe(const int8_t *A, const int8_t *Bt, int *D, hipStream_t stream);
+
+// ---- missing calls of the exact-integer path: index lists, gather-sums, row shuffles (missing_kernels.hip) ----
+// the hybrid missing-indicator route's row shuffles
 void gather_packed_rows(const uint8_t *src, size_t pitch, const uint32_t *idx, uint32_t nidx, uint32_t rows_out, uint8_t *dst, hipStream_t stream);
 void patch_missing_rows(uint8_t *packed, size_t pitch, const uint32_t *idx, uint32_t nidx, hipStream_t stream);
 void scatter_packed_rows(const uint8_t *src, size_t pitch, const uint32_t *idx, uint32_t nidx, uint8_t *packed, hipStream_t stream);
@@ -179,14 +193,6 @@ void sparse_rows_sum_f32(const uint32_t *ptr, const uint32_t *idx, const float *
 // which kernel the two launches above take for these arguments (rowscale: a per-row factor is given): 1 one wave per row, 2 the same
 // with batched index reads, 3 several rows per wave
 int sparse_rows_sum_variant(int b, bool rowscale, bool short_lists, double avg_len);
-void i8_rowscales(const double *mean, const double *sd, uint64_t P_g, uint64_t P_pad, double *inv_sd, double *mu_inv_sd,
-                  hipStream_t stream);
-void transpose_packed(const uint8_t *in, size_t pitch_in, uint64_t N_pad, uint64_t P_pad, uint8_t *out, size_t pitch_out,
-                      hipStream_t stream, bool tiled = false /* write the band-tiled layout */);
-// out = the band-tiled arrangement of the row-major records in[rows][pitch] (rows a multiple of 32, pitch of 64)
-void tile_packed(const uint8_t *in, size_t pitch, uint64_t rows, uint8_t *out, hipStream_t stream);
-double mfma_i8_peak_tops(int waves_per_simd, int iters, uint32_t fill, hipStream_t stream);
-void mfma_i8_probe(const int8_t *A, const int8_t *Bt, int *D, hipStream_t stream);
 
 } // namespace kern
 } // namespace fpca

@@ -26,6 +26,7 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "launch_check.hpp"
 
 namespace fpca {
 namespace kern {
@@ -35,12 +36,6 @@ typedef int v16i __attribute__((ext_vector_type(16)));
 typedef double d2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u2 __attribute__((ext_vector_type(2)));
-
-#define HIP_CHECK_LAUNCH()                                                                         \
-   do {                                                                                             \
-      hipError_t e__ = hipGetLastError();                                                           \
-      if (e__ != hipSuccess) throw Error(-3, std::string("kernel launch failed: ") + hipGetErrorString(e__)); \
-   } while (0)
 
 // ------------------------------------------------------------------------------------------------
 // slicing of an fp64 operand V[rows_pad][b] (row-major, rows = samples for K2, SNPs for K3) into
@@ -215,7 +210,7 @@ void i8_colmax(const double *V, uint64_t rows, int b, int nops, const SliceOp *o
                          ops[1].maxbits);
    else
       hipLaunchKernelGGL(k_colmax<1>, dim3(blocks), dim3(256), 0, stream, V, rows, b, ops[0].rowscale, ops[0].maxbits, nullptr, nullptr);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 void i8_slice(const double *V, uint64_t rows_pad, uint64_t rows, int b, int S, int nops, const SliceOp *ops, hipStream_t stream)
@@ -227,7 +222,7 @@ void i8_slice(const double *V, uint64_t rows_pad, uint64_t rows, int b, int S, i
       hipLaunchKernelGGL(k_slice<2>, dim3(blocks), dim3(256), 0, stream, V, rows_pad, rows, b, S, nsc, ops[0], ops[1]);
    else
       hipLaunchKernelGGL(k_slice<1>, dim3(blocks), dim3(256), 0, stream, V, rows_pad, rows, b, S, nsc, ops[0], ops[0]);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -429,12 +424,12 @@ __global__ __launch_bounds__(256) void k_dequant_rows(const int8_t *__restrict__
 void i8_maxbits_fold(const unsigned long long *bits, double *out64, hipStream_t stream)
 {
    hipLaunchKernelGGL(k_maxbits_fold, dim3(1), dim3(64), 0, stream, bits, out64);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 void i8_maxbits_set(const double *all, int G, unsigned long long *bits, hipStream_t stream)
 {
    hipLaunchKernelGGL(k_maxbits_set, dim3(1), dim3(64), 0, stream, all, G, bits);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 void i8_slice_rows(const double *V, uint64_t rows, int b, int S, const SliceOp &op, int8_t *Qrm, hipStream_t stream)
 {
@@ -442,7 +437,7 @@ void i8_slice_rows(const double *V, uint64_t rows, int b, int S, const SliceOp &
    if (!rows) return;
    const uint64_t threads = rows * (b / 16);
    hipLaunchKernelGGL(k_slice_rows, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, V, rows, b, S, gemm_i8_nsc_pad(S, b), op.maxbits, Qrm, op.colw);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 void i8_unpack_slices(const int8_t *Qrm, uint64_t rows_pad, int b, int S, const SliceOp &op, hipStream_t stream, uint64_t rows_valid, float *copy32,
                       double *copy64)
@@ -459,14 +454,14 @@ void i8_unpack_slices(const int8_t *Qrm, uint64_t rows_pad, int b, int S, const 
    }
    hipLaunchKernelGGL(k_unpack_slices, dim3((unsigned)((groups + trg - 1) / trg)), dim3(256), lds, stream, Qrm, rows_pad, b, S, trg, op.Q, op.colsum, op.maxbits,
                       rows_valid, copy32, copy64);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 void i8_dequant_rows(const int8_t *Qrm, uint64_t rows, int b, int S, const SliceOp &op, float *copy32, double *copy64, hipStream_t stream)
 {
    if (!rows) return;
    const uint64_t threads = rows * (b / 16);
    hipLaunchKernelGGL(k_dequant_rows, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, Qrm, rows, b, S, op.maxbits, copy32, copy64);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1111,6 +1106,63 @@ __global__ __launch_bounds__(256) void k_i8_combine(const double *__restrict__ p
    }
 }
 
+// ---- the instances ----
+// Every k_gemm_i8<I8Cfg<...>> there is, once.  The shape rules below ask this list what exists, gemm_i8 looks its kernel up in it, and
+// the static_assert behind i8_shape_static refuses to compile a shape without an instance.  All are KC = 256, waves WR x 1.
+template <class... C>
+struct I8List {};
+constexpr bool I8_RM = false, I8_TL = true; // layout of `packed`: row-major / band-tiled (I8Cfg::TILED)
+constexpr bool I8_HALF = true;
+// two operands (K3): 64-row waves
+template <int NT, int MODE, bool TILED, bool HALF = false>
+using I8Two = I8Cfg<true, 2, NT, 4, 1, 256, 1, MODE, HALF, TILED>;
+// one operand, G.M alone (I8_NO_MISSING): 64-row waves, 4 of them or 8
+template <int NT, bool TILED, bool HALF = false, int WR = 4>
+using I8One = I8Cfg<false, 2, NT, WR, 1, 256, 1, I8_NO_MISSING, HALF, TILED>;
+// one operand, both matrices (K2, dense missing-indicator routes), row-major only: 64-row waves in a narrow column block (<= 3 tiles) and
+// for the half tile; from 4 tiles up 32-row waves, the tiles in 2 groups
+template <int NT, int MODE, bool HALF = false>
+using I8Both = I8Cfg<false, (NT <= 3 || HALF) ? 2 : 1, NT, 4, 1, 256, (NT <= 3 || HALF) ? 1 : 2, MODE, HALF, I8_RM>;
+using I8Instances = I8List<
+   I8Two<2, I8_FULL, I8_RM>, I8Two<3, I8_FULL, I8_RM>, I8Two<4, I8_FULL, I8_RM>, I8Two<4, I8_FULL, I8_RM, I8_HALF>,
+   I8Two<2, I8_FULL, I8_TL>, I8Two<3, I8_FULL, I8_TL>, I8Two<4, I8_FULL, I8_TL>, I8Two<4, I8_FULL, I8_TL, I8_HALF>,
+   I8Two<2, I8_SKIP_EMPTY, I8_RM>, I8Two<3, I8_SKIP_EMPTY, I8_RM>, I8Two<4, I8_SKIP_EMPTY, I8_RM>,
+   I8Two<2, I8_SKIP_EMPTY, I8_TL>, I8Two<3, I8_SKIP_EMPTY, I8_TL>, I8Two<4, I8_SKIP_EMPTY, I8_TL>,
+   I8One<2, I8_RM>, I8One<3, I8_RM>, I8One<4, I8_RM>, I8One<5, I8_RM>, I8One<6, I8_RM>, I8One<7, I8_RM>, I8One<8, I8_RM>,
+   I8One<2, I8_TL>, I8One<3, I8_TL>, I8One<4, I8_TL>, I8One<5, I8_TL>, I8One<6, I8_TL>, I8One<7, I8_TL>, I8One<8, I8_TL>,
+   I8One<2, I8_RM, I8_HALF>, I8One<4, I8_RM, I8_HALF>, I8One<2, I8_TL, I8_HALF>, I8One<4, I8_TL, I8_HALF>,
+   I8One<2, I8_RM, false, 8>, I8One<4, I8_RM, I8_HALF, 8>, I8One<2, I8_TL, false, 8>, I8One<4, I8_TL, I8_HALF, 8>, // 512 rows
+   I8Both<2, I8_FULL>, I8Both<3, I8_FULL>, I8Both<4, I8_FULL>, I8Both<5, I8_FULL>, I8Both<6, I8_FULL>, I8Both<7, I8_FULL>, I8Both<8, I8_FULL>,
+   I8Both<4, I8_FULL, I8_HALF>,
+   I8Both<2, I8_SKIP_EMPTY>, I8Both<3, I8_SKIP_EMPTY>, I8Both<4, I8_SKIP_EMPTY>, I8Both<5, I8_SKIP_EMPTY>, I8Both<6, I8_SKIP_EMPTY>,
+   I8Both<7, I8_SKIP_EMPTY>, I8Both<8, I8_SKIP_EMPTY>>;
+
+// what tells two instances apart: the operands, the matrices, the column block, the tile height and the layout of `packed`
+struct I8Key {
+   bool two;
+   int mode, nt;
+   bool half;
+   int rows;
+   bool tiled;
+};
+// f(C{}) for the instance C with this key, and its answer; false if there is none
+template <class... C, class F>
+constexpr bool i8_find(I8List<C...>, const I8Key &k, F &&f)
+{
+   return ((k.two == C::TWO && k.mode == C::MODE && k.nt == C::NT && k.half == C::HALF && k.rows == C::ROWS && k.tiled == C::TILED && f(C{})) || ...);
+}
+constexpr bool i8_exists(bool two, int mode, int nt, bool half, int rows, bool tiled)
+{
+   return i8_find(I8Instances{}, I8Key{two, mode, nt, half, rows, tiled}, [](auto) { return true; });
+}
+// tile height of the 4-wave instance of (two, mode, nt, half), whatever the layout; 0: there is none
+constexpr int i8_rows4(bool two, int mode, int nt, bool half)
+{
+   for (int rows = 256; rows >= 128; rows -= 128)
+      if (i8_exists(two, mode, nt, half, rows, I8_RM) || i8_exists(two, mode, nt, half, rows, I8_TL)) return rows;
+   return 0;
+}
+
 // ---- shape selection ----
 // The slice-columns (S*b, rounded up to whole 32-column tiles) are cut into `zb` equal column blocks of NT tiles
 // (blockIdx.z); 4 x 1 waves per workgroup, KC = 256:
@@ -1167,30 +1219,56 @@ static int i8_tile_rows(uint64_t rows_pad, int ncu, const I8Shape &sh)
    return (sh.half && sh.nt == 4 && tiles512 * 4 >= (uint64_t)I8_WIDE_QUARTERS * ncu) ? 512 : sh.rows;
 }
 
-// rows_pad: the rows of the launch the shape is for (0: the 4-wave shape, whatever the launch)
-static I8Shape i8_shape(int S, int b, bool two, int mode = I8_FULL, uint64_t rows_pad = 0)
+// the 4-wave shape, whatever the launch and the device
+constexpr I8Shape i8_shape_static(int S, int b, bool two, int mode)
 {
    const int tiles = (S * b + 31) / 32, cap = two ? 4 : 8; // largest instantiated block
    // smallest instantiated block: 2 tiles (few slices of a narrow block: S = 4, b = 16 is 64 slice-columns).  Rounds 2-5 had the
    // two-matrix kernels from 4 (K2) / 3 (K3) tiles up only: the eigensolver's 4-slice passes on data whose missing calls take the dense
    // route multiplied 2 / 1 tiles of zero padding per launch (profiles/r06_missing_routes.txt)
-   I8Shape sh;
+   I8Shape sh{};
    sh.zb = (tiles + cap - 1) / cap;
    sh.nt = std::max(2, (tiles + sh.zb - 1) / sh.zb);
-   // one matrix only (I8_NO_MISSING), or both in a narrow column block: the accumulators fit a second row tile per wave (64 rows x
-   // NT tiles)
-   sh.rows = (two || mode == I8_NO_MISSING || sh.nt <= 3) ? 256 : 128;
-   sh.cols = 32 * sh.nt;
-   sh.kc = 256;
    // b = 16 with S = 7 slices: 112 slice-columns = 3.5 tiles -- the one-matrix kernel (the default route up to 0.5 % missing
    // calls) takes the remainder as a half tile
    // ... and so does b = 16 with S = 3 (48 slice-columns = 1.5 tiles: the eigensolver's cheap passes, one-matrix kernel only)
-   sh.half = mode != I8_SKIP_EMPTY && sh.zb == 1 && S * b == 32 * sh.nt - 16 && (sh.nt == 4 || (sh.nt == 2 && !two && mode == I8_NO_MISSING));
-   if (sh.half) {
-      sh.cols -= 16;
-      sh.rows = 256; // (every half-tile instantiation is 4 or 8 waves x 64 rows, the two-matrix K2 one included)
-   }
-   sh.wide = !two && mode == I8_NO_MISSING && sh.zb == 1 && ((sh.nt == 4 && sh.half) || (sh.nt == 2 && !sh.half));
+   sh.half = sh.zb == 1 && S * b == 32 * sh.nt - 16 && i8_rows4(two, mode, sh.nt, I8_HALF) != 0;
+   // one matrix only (I8_NO_MISSING), both in a narrow column block, or a half tile: the accumulators fit a second row tile per wave
+   // (64 rows x NT tiles)
+   sh.rows = i8_rows4(two, mode, sh.nt, sh.half);
+   sh.cols = 32 * sh.nt - (sh.half ? 16 : 0);
+   sh.kc = 256;
+   sh.wide = i8_exists(two, mode, sh.nt, sh.half, 512, I8_RM) || i8_exists(two, mode, sh.nt, sh.half, 512, I8_TL);
+   return sh;
+}
+
+// Every shape gemm_i8 can be asked for has its instance -- same key, same tile -- in every layout gemm_i8 accepts for it, and at 512
+// rows too where the shape says so
+constexpr bool i8_shapes_have_instances()
+{
+   for (int S = 2; S <= 8; S++)
+      for (int b = 16; b <= 64; b += 16)
+         for (int two = 0; two < 2; two++)
+            for (int mode = I8_FULL; mode <= I8_NO_MISSING; mode++) {
+               if (two && mode == I8_NO_MISSING) continue;
+               const I8Shape sh = i8_shape_static(S, b, two, mode);
+               const auto has = [&](int rows, bool tiled) {
+                  return i8_find(I8Instances{}, I8Key{two != 0, mode, sh.nt, sh.half, rows, tiled},
+                                 [&](auto c) { return decltype(c)::COLS == sh.cols && decltype(c)::KC == sh.kc; });
+               };
+               for (int tiled = 0; tiled < 2; tiled++) {
+                  if (tiled && !two && mode != I8_NO_MISSING) continue; // (gemm_i8 refuses it)
+                  if (!has(sh.rows, tiled != 0) || (sh.wide && !has(512, tiled != 0))) return false;
+               }
+            }
+   return true;
+}
+static_assert(i8_shapes_have_instances(), "a shape of i8_shape_static has no k_gemm_i8 instance: see I8Instances");
+
+// rows_pad: the rows of the launch the shape is for (0: the 4-wave shape, whatever the launch)
+static I8Shape i8_shape(int S, int b, bool two, int mode = I8_FULL, uint64_t rows_pad = 0)
+{
+   I8Shape sh = i8_shape_static(S, b, two, mode);
    if (rows_pad) sh.rows = i8_tile_rows(rows_pad, i8_ncu(), sh);
    return sh;
 }
@@ -1273,6 +1351,12 @@ static int i8_bw(int b) // lcm(32, b) for b in {16, 32, 48, 64}
    return b == 48 ? 96 : std::max(b, 32);
 }
 
+// doubles of the workspace a plan uses: plane 0 of every row, planes 1 .. sB-1 of the phase-B rows
+static size_t i8_plan_doubles(const I8Plan &p, uint64_t rows_pad, int zb, int bw)
+{
+   return ((size_t)rows_pad + (size_t)(p.sB - 1) * p.rowsB) * zb * 2 * (size_t)bw;
+}
+
 size_t gemm_i8_workspace_doubles(uint64_t rows_pad, uint64_t k_pad, int S, int b, bool two)
 {
    size_t need = 0;
@@ -1280,7 +1364,7 @@ size_t gemm_i8_workspace_doubles(uint64_t rows_pad, uint64_t k_pad, int S, int b
       if (two && mode == I8_NO_MISSING) continue;
       const I8Shape sh = i8_shape(S, b, two, mode, rows_pad); // (the tile height gemm_i8 will choose for these rows)
       const I8Plan p = i8_plan(rows_pad, k_pad, sh, i8_bw(b));
-      need = std::max(need, ((size_t)rows_pad + (size_t)(p.sB - 1) * p.rowsB) * sh.zb * 2 * (size_t)i8_bw(b));
+      need = std::max(need, i8_plan_doubles(p, rows_pad, sh.zb, i8_bw(b)));
    }
    return need;
 }
@@ -1323,74 +1407,21 @@ void gemm_i8(const uint8_t *packed, size_t pitch, const int8_t *Qg, const int8_t
    // 1 .. sB-1 of the phase-B rows -- so that a partial the kernel fails to write cannot pass for the previous launch's value
    static const bool poison = FPCA_TEST_ENV("FPCA_DEBUG_I8_POISON") != nullptr;
    if (poison) {
-      const size_t used = ((size_t)rows_pad + (size_t)(pl.sB - 1) * pl.rowsB) * sh.zb * 2 * (size_t)bw;
+      const size_t used = i8_plan_doubles(pl, rows_pad, sh.zb, bw);
       if (hipMemsetAsync(ws, 0xFF, used * sizeof(double), stream) != hipSuccess) throw Error(-3, "gemm_i8: poisoning the workspace failed");
    }
-#define FPCA_I8_ARGS pl, stream, packed, pitch, Qg, Qm, k_pad, wg, wm, bw, ws, rows_pad, chunks_total, sh.zb, (e_only ? 0x00000100u : 0x00010002u)
    if (gemm_events) (void)hipEventRecord(gemm_events[0], stream);
    if (two && mode == I8_NO_MISSING) throw Error(-1, "gemm_i8: without missing genotypes both matrices share one operand (pass Qm == Qg)");
-// (TL: the instance for the band-tiled layout -- every kernel that reads the sample-major copy, and the G.M-alone K2 kernels)
-#define FPCA_I8_K3(NT_, MODE_) launch_i8<I8Cfg<true, 2, NT_, 4, 1, 256, 1, MODE_, false, TL>>(FPCA_I8_ARGS)
-// one matrix, or both in a narrow column block (<= 3 tiles): 64-row waves; both from 4 tiles up: 32-row waves, the tiles in 2 groups
-#define FPCA_I8_K2(NT_, MODE_)                                                                                               \
-   launch_i8<I8Cfg<false, (MODE_ == I8_NO_MISSING || NT_ <= 3 ? 2 : 1), NT_, 4, 1, 256, (MODE_ == I8_NO_MISSING || NT_ <= 3 ? 1 : 2), \
-                   MODE_, false, TL>>(FPCA_I8_ARGS)
-#define FPCA_I8_K3_NT(MODE_)                       \
-   switch (sh.nt) {                                \
-   case 2: FPCA_I8_K3(2, MODE_); break;            \
-   case 3: FPCA_I8_K3(3, MODE_); break;            \
-   default: FPCA_I8_K3(4, MODE_); break;           \
-   }
-#define FPCA_I8_K2_NT(MODE_)                       \
-   switch (sh.nt) {                                \
-   case 2: FPCA_I8_K2(2, MODE_); break;            \
-   case 3: FPCA_I8_K2(3, MODE_); break;            \
-   case 4: FPCA_I8_K2(4, MODE_); break;            \
-   case 5: FPCA_I8_K2(5, MODE_); break;            \
-   case 6: FPCA_I8_K2(6, MODE_); break;            \
-   case 7: FPCA_I8_K2(7, MODE_); break;            \
-   default: FPCA_I8_K2(8, MODE_); break;           \
-   }
-   auto run = [&](auto tl) {
-      constexpr bool TL = decltype(tl)::value;
-      if (two) {
-         if (sh.half)
-            launch_i8<I8Cfg<true, 2, 4, 4, 1, 256, 1, I8_FULL, true, TL>>(FPCA_I8_ARGS);
-         else if (mode == I8_SKIP_EMPTY)
-            FPCA_I8_K3_NT(I8_SKIP_EMPTY)
-         else
-            FPCA_I8_K3_NT(I8_FULL)
-      } else if (mode == I8_NO_MISSING) {
-         if (sh.rows == 512 && sh.half) // 8 waves, 512 rows (i8_tile_rows)
-            launch_i8<I8Cfg<false, 2, 4, 8, 1, 256, 1, I8_NO_MISSING, true, TL>>(FPCA_I8_ARGS);
-         else if (sh.rows == 512)
-            launch_i8<I8Cfg<false, 2, 2, 8, 1, 256, 1, I8_NO_MISSING, false, TL>>(FPCA_I8_ARGS);
-         else if (sh.half && sh.nt == 2)
-            launch_i8<I8Cfg<false, 2, 2, 4, 1, 256, 1, I8_NO_MISSING, true, TL>>(FPCA_I8_ARGS);
-         else if (sh.half)
-            launch_i8<I8Cfg<false, 2, 4, 4, 1, 256, 1, I8_NO_MISSING, true, TL>>(FPCA_I8_ARGS);
-         else
-            FPCA_I8_K2_NT(I8_NO_MISSING)
-      } else if constexpr (!TL) { // both matrices against one operand (K2, dense missing-indicator routes): row-major only
-         if (mode == I8_SKIP_EMPTY) {
-            FPCA_I8_K2_NT(I8_SKIP_EMPTY)
-         } else if (sh.half) {
-            launch_i8<I8Cfg<false, 2, 4, 4, 1, 256, 1, I8_FULL, true>>(FPCA_I8_ARGS);
-         } else {
-            FPCA_I8_K2_NT(I8_FULL)
-         }
-      }
-   };
-   if (tiled)
-      run(std::true_type{});
-   else
-      run(std::false_type{});
-#undef FPCA_I8_K2_NT
-#undef FPCA_I8_K3_NT
-#undef FPCA_I8_K2
-#undef FPCA_I8_K3
-#undef FPCA_I8_ARGS
-   HIP_CHECK_LAUNCH();
+   // the instance of this shape at the tile height chosen for these rows, for the layout of `packed`: plan, kernel and combine then
+   // walk the same tile grid
+   const bool launched = i8_find(I8Instances{}, I8Key{two, mode, sh.nt, sh.half, sh.rows, tiled}, [&](auto c) {
+      using C = decltype(c);
+      if (C::COLS != sh.cols || C::KC != sh.kc) throw Error(-1, "gemm_i8: the kernel instance and the shape disagree about the tile");
+      launch_i8<C>(pl, stream, packed, pitch, Qg, Qm, k_pad, wg, wm, bw, ws, rows_pad, chunks_total, sh.zb, (e_only ? 0x00000100u : 0x00010002u));
+      return true;
+   });
+   if (!launched) throw Error(-1, "gemm_i8: no kernel instance for this shape");
+   launch_check();
    if (gemm_events) (void)hipEventRecord(gemm_events[1], stream);
    if (before_combine) (void)hipStreamWaitEvent(stream, before_combine, 0);
    const unsigned blocks = (unsigned)std::min<uint64_t>(1024, (rows_pad + (256 / b) - 1) / (256 / b));
@@ -1398,7 +1429,7 @@ void gemm_i8(const uint8_t *packed, size_t pitch, const int8_t *Qg, const int8_t
                       mean, sd, out,
                       next_ops ? next_ops[0].rowscale : nullptr, next_ops ? next_ops[0].maxbits : nullptr,
                       next_ops ? next_ops[1].rowscale : nullptr, next_ops ? next_ops[1].maxbits : nullptr);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 // per-SNP row scales of the K3 operands: inv_sd = 1/sd (0 for a monomorphic SNP, sd <= 1e-9, like the lookup table of
@@ -1421,393 +1452,7 @@ void i8_rowscales(const double *mean, const double *sd, uint64_t P_g, uint64_t P
                   hipStream_t stream)
 {
    hipLaunchKernelGGL(k_i8_rowscales, dim3((unsigned)((P_pad + 255) / 256)), dim3(256), 0, stream, mean, sd, P_g, P_pad, inv_sd, mu_inv_sd);
-   HIP_CHECK_LAUNCH();
-}
-
-// ------------------------------------------------------------------------------------------------
-// Sparse missing indicator.  With a typical array-data missing rate (0.1 %) the E half of the int8 work multiplies a
-// matrix that is 99.9 % zeros.  Instead: index lists of the missing calls (per SNP for K2, per sample for K3), built
-// once, and  E'B  /  E (mean T / sd)  as gathers of fp64 rows -- 256 bytes per missing call, a few ms where the MFMA
-// route took 8-9 -- while the int8 GEMM multiplies G.M alone with the one-matrix kernel.
-
-// missing calls of each 2-bit record among its first `ncols` codes
-// (tiled: the records are in the band-tiled layout -- byte j of a record sits in its 16-byte piece j / 16)
-__global__ __launch_bounds__(256) void k_count_missing(const uint8_t *__restrict__ packed, size_t pitch, uint64_t ncols,
-                                                        uint32_t *__restrict__ cnt, bool tiled)
-{
-   const uint64_t rec = blockIdx.x;
-   auto byte_at = [&](uint64_t j) { return packed + packed_piece_offset(rec, j >> 4, pitch, tiled) + (j & 15); };
-   const uint64_t nbytes = (ncols + 3) / 4, nw = nbytes / 4;
-   uint32_t n = 0;
-   for (uint64_t i = threadIdx.x; i < nw; i += 256) {
-      const uint32_t w = *reinterpret_cast<const uint32_t *>(byte_at(4 * i));
-      n += __popc(w & ~(w >> 1) & 0x55555555u);
-   }
-   for (uint64_t i = nw * 4 + threadIdx.x; i < nbytes; i += 256) {
-      const uint32_t w = *byte_at(i);
-      n += __popc(w & ~(w >> 1) & 0x55u);
-   }
-   // codes beyond ncols in the last byte
-   if (threadIdx.x == 0 && (ncols & 3)) {
-      const uint32_t w = *byte_at(nbytes - 1) >> (2 * (ncols & 3));
-      n -= __popc(w & ~(w >> 1) & 0x55u);
-   }
-   __shared__ uint32_t red[256];
-   red[threadIdx.x] = n;
-   __syncthreads();
-   for (int o = 128; o > 0; o >>= 1) {
-      if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-      __syncthreads();
-   }
-   if (threadIdx.x == 0) cnt[blockIdx.x] = red[0];
-}
-
-// idx[ptr[r] ..] = ascending positions (< ncols) of the missing calls of record r.  The record is walked in tiles of 1024
-// dwords (coalesced 16-byte loads), every thread owns four consecutive dwords = 64 codes; a wave scan + 4 wave totals
-// place each thread's hits.  (Rows are 128-byte aligned and padded with "missing" codes up to the pitch, so whole
-// 16-byte pieces can be read; positions >= ncols are masked off.)
-__global__ __launch_bounds__(256) void k_fill_missing(const uint8_t *__restrict__ packed, size_t pitch, uint64_t ncols,
-                                                       const uint32_t *__restrict__ ptr, uint32_t *__restrict__ idx, bool tiled)
-{
-   const uint64_t nq = (ncols + 63) / 64; // 16-byte pieces holding valid codes
-   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-   __shared__ uint32_t wsum[4];
-   uint32_t base = ptr[blockIdx.x];
-   if (ptr[blockIdx.x + 1] == base) return; // nothing to list: a record without a missing call -- or one whose missing calls go the
-                                            // dense route (its count was set to zero on purpose, device_ctx.hip ensure_hybrid)
-   for (uint64_t q0 = 0; q0 < nq; q0 += 256) {
-      const uint64_t q = q0 + threadIdx.x;
-      uint32_t m[4] = {0u, 0u, 0u, 0u};
-      if (q < nq) {
-         const u4 x = *reinterpret_cast<const u4 *>(packed + packed_piece_offset(blockIdx.x, q, pitch, tiled));
-#pragma unroll
-         for (int k = 0; k < 4; k++) {
-            m[k] = x[k] & ~(x[k] >> 1) & 0x55555555u;
-            const uint64_t first = q * 64 + 16 * k; // first code of this dword
-            if (first >= ncols)
-               m[k] = 0u;
-            else if (ncols - first < 16)
-               m[k] &= (1u << (2 * (ncols - first))) - 1u;
-         }
-      }
-      const uint32_t c = __popc(m[0]) + __popc(m[1]) + __popc(m[2]) + __popc(m[3]);
-      uint32_t v = c;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-         const uint32_t t = __shfl_up(v, o);
-         if (lane >= o) v += t;
-      }
-      if (lane == 63) wsum[wave] = v;
-      __syncthreads();
-      uint32_t woff = 0, total = 0;
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-         if (k < wave) woff += wsum[k];
-         total += wsum[k];
-      }
-      uint32_t pos = base + woff + v - c;
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-         uint32_t mk = m[k];
-         while (mk) {
-            const int bit = __ffs(mk) - 1;
-            idx[pos++] = (uint32_t)(q * 64 + 16 * k + bit / 2);
-            mk &= mk - 1;
-         }
-      }
-      base += total;
-      __syncthreads();
-   }
-}
-
-void count_missing(const uint8_t *packed, size_t pitch, uint64_t ncols, uint64_t nrec, uint32_t *cnt, hipStream_t stream, bool tiled)
-{
-   if (!nrec) return;
-   hipLaunchKernelGGL(k_count_missing, dim3((unsigned)nrec), dim3(256), 0, stream, packed, pitch, ncols, cnt, tiled);
-   HIP_CHECK_LAUNCH();
-}
-
-void fill_missing(const uint8_t *packed, size_t pitch, uint64_t ncols, uint64_t nrec, const uint32_t *ptr, uint32_t *idx, hipStream_t stream,
-                  bool tiled)
-{
-   if (!nrec) return;
-   hipLaunchKernelGGL(k_fill_missing, dim3((unsigned)nrec), dim3(256), 0, stream, packed, pitch, ncols, ptr, idx, tiled);
-   HIP_CHECK_LAUNCH();
-}
-
-// out[r][c] = sum over s in list(r) of V[s][c] * (rowscale ? rowscale[s] : 1)   (fp64, list order = ascending s);
-// rows r >= nrec are zeroed.  One wave per output row; EPW = 64 / b list entries per step, 4 steps in flight.
-template <int B, class VT>
-__global__ __launch_bounds__(256) void k_sparse_rows_sum(const uint32_t *__restrict__ ptr, const uint32_t *__restrict__ idx,
-                                                          const VT *__restrict__ V, const double *__restrict__ rowscale, uint64_t nrec,
-                                                          uint64_t rows_out, double *__restrict__ out, const double *__restrict__ init,
-                                                          const double *__restrict__ colw)
-{
-   constexpr int EPW = 64 / B;
-   const int lane = threadIdx.x & 63, c = lane % B, e0 = lane / B;
-   for (uint64_t r = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows_out; r += (uint64_t)gridDim.x * 4) {
-      double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-      if (r < nrec) {
-         const uint32_t p0 = ptr[r], p1 = ptr[r + 1];
-         for (uint32_t t = p0 + e0; t < p1; t += 4 * EPW) {
-            const uint32_t t1 = t + EPW, t2 = t + 2 * EPW, t3 = t + 3 * EPW;
-            const uint32_t s0 = idx[t], s1 = t1 < p1 ? idx[t1] : 0, s2 = t2 < p1 ? idx[t2] : 0, s3 = t3 < p1 ? idx[t3] : 0;
-            double v0 = V[(uint64_t)s0 * B + c], v1 = t1 < p1 ? V[(uint64_t)s1 * B + c] : 0.0, v2 = t2 < p1 ? V[(uint64_t)s2 * B + c] : 0.0,
-                   v3 = t3 < p1 ? V[(uint64_t)s3 * B + c] : 0.0;
-            if (rowscale) {
-               v0 *= rowscale[s0];
-               v1 *= t1 < p1 ? rowscale[s1] : 0.0;
-               v2 *= t2 < p1 ? rowscale[s2] : 0.0;
-               v3 *= t3 < p1 ? rowscale[s3] : 0.0;
-            }
-            a0 += v0;
-            a1 += v1;
-            a2 += v2;
-            a3 += v3;
-         }
-      }
-      double a = (a0 + a1) + (a2 + a3);
-#pragma unroll
-      for (int o = 32; o >= B; o >>= 1) a += __shfl_down(a, o);
-      if (lane < B) {
-         if (colw) a *= colw[c] * 32.0; // fp32 rows were stored as x 2^(1 - e_c); colw[c] = 2^(e_c - 6) (top slice's weight)
-         out[r * B + c] = init ? init[r * B + c] + a : a;
-      }
-   }
-}
-
-// The same sum with the index list read in coalesced batches of 64 (one entry per lane, broadcast by shuffles) instead of
-// one dependent 4-byte load per gathered row: the loop above is a chain idx -> row of V, both at Infinity-Cache latency,
-// with four rows in flight per wave; here the rows of a batch are independent of any further index load and eight of them
-// are in flight (per lane slot).  The per-row factors of a batch are gathered once, one per lane, the same way.
-template <int B, class VT>
-__global__ __launch_bounds__(256) void k_sparse_rows_sum_batched(const uint32_t *__restrict__ ptr, const uint32_t *__restrict__ idx,
-                                                                  const VT *__restrict__ V, const double *__restrict__ rowscale,
-                                                                  uint64_t nrec, uint64_t rows_out, double *__restrict__ out, const double *__restrict__ init,
-                                                                  const double *__restrict__ colw)
-{
-   constexpr int EPW = 64 / B, U = 8;
-   const int lane = threadIdx.x & 63, c = lane % B, e0 = lane / B;
-   for (uint64_t r = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows_out; r += (uint64_t)gridDim.x * 4) {
-      double acc[U];
-#pragma unroll
-      for (int u = 0; u < U; u++) acc[u] = 0.0;
-      if (r < nrec) {
-         const uint32_t p0 = ptr[r], p1 = ptr[r + 1];
-         for (uint32_t t0 = p0; t0 < p1; t0 += 64) {
-            const int cnt = (int)(p1 - t0 < 64u ? p1 - t0 : 64u);
-            const uint32_t mine = lane < cnt ? idx[t0 + lane] : 0u;
-            const double myscale = (rowscale && lane < cnt) ? rowscale[mine] : 1.0;
-            for (int u0 = 0; u0 < cnt; u0 += EPW * U) {
-#pragma unroll
-               for (int u = 0; u < U; u++) {
-                  const int e = u0 + u * EPW + e0;
-                  const uint32_t srow = (uint32_t)__shfl((int)mine, e & 63);
-                  const double sc = __shfl(myscale, e & 63);
-                  if (e < cnt) acc[u] += V[(uint64_t)srow * B + c] * sc;
-               }
-            }
-         }
-      }
-      double a = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
-#pragma unroll
-      for (int o = 32; o >= B; o >>= 1) a += __shfl_down(a, o);
-      if (lane < B) {
-         if (colw) a *= colw[c] * 32.0; // fp32 rows were stored as x 2^(1 - e_c); colw[c] = 2^(e_c - 6) (top slice's weight)
-         out[r * B + c] = init ? init[r * B + c] + a : a;
-      }
-   }
-}
-
-// Short lists (a dozen entries per row: the samples of a 1/8 SNP shard, small problems): with one wave per row the chain
-// ptr -> idx -> rows is three dependent round trips per row and nothing else in flight in that wave -- latency-bound (4 TB/s
-// out of an L2-resident operand).  Here 64 / B rows share a wave, B lanes (one per column) each, every group walking its own
-// list four entries at a time: four times the rows in flight, no cross-lane reduction.
-template <int B, class VT>
-__global__ __launch_bounds__(256) void k_sparse_rows_sum_short(const uint32_t *__restrict__ ptr, const uint32_t *__restrict__ idx,
-                                                                const VT *__restrict__ V, uint64_t nrec, uint64_t rows_out,
-                                                                double *__restrict__ out, const double *__restrict__ init,
-                                                                const double *__restrict__ colw)
-{
-   constexpr int G = 64 / B;
-   const int lane = threadIdx.x & 63, c = lane % B, g = lane / B;
-   for (uint64_t r0 = ((uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * G; r0 < rows_out; r0 += (uint64_t)gridDim.x * 4 * G) {
-      const uint64_t r = r0 + g;
-      double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-      uint32_t p0 = 0, p1 = 0;
-      if (r < nrec) {
-         p0 = ptr[r];
-         p1 = ptr[r + 1];
-      }
-      // the group's index list in batches of B (one coalesced read, an entry per lane, handed round by shuffles): the row reads of
-      // a batch do not wait for any further index read.  (Groups of a wave may run a different number of batches: the shuffles
-      // are executed by all lanes, the reads are predicated.)
-      uint32_t longest = p1 - p0;
-#pragma unroll
-      for (int o = 32; o >= B; o >>= 1) longest = max(longest, (uint32_t)__shfl_xor((int)longest, o));
-      for (uint32_t base = 0; base < longest; base += B) {
-         const uint32_t t = p0 + base + c;
-         const int cnt = (int)min((uint32_t)B, p1 - p0 > base ? p1 - p0 - base : 0u);
-         const uint32_t mine = t < p1 ? idx[t] : 0u;
-#pragma unroll
-         for (int e = 0; e < B; e += 4) {
-            const uint32_t s0 = (uint32_t)__shfl((int)mine, g * B + e), s1 = (uint32_t)__shfl((int)mine, g * B + e + 1),
-                           s2 = (uint32_t)__shfl((int)mine, g * B + e + 2), s3 = (uint32_t)__shfl((int)mine, g * B + e + 3);
-            if (e < cnt) a0 += (double)V[(uint64_t)s0 * B + c];
-            if (e + 1 < cnt) a1 += (double)V[(uint64_t)s1 * B + c];
-            if (e + 2 < cnt) a2 += (double)V[(uint64_t)s2 * B + c];
-            if (e + 3 < cnt) a3 += (double)V[(uint64_t)s3 * B + c];
-         }
-      }
-      if (r < rows_out) {
-         double a = (a0 + a1) + (a2 + a3);
-         if (colw) a *= colw[c] * 32.0;
-         out[r * B + c] = init ? init[r * B + c] + a : a;
-      }
-   }
-}
-
-// The gather kernel a launch takes: 1 = k_sparse_rows_sum, 2 = k_sparse_rows_sum_batched, 3 = k_sparse_rows_sum_short (which exists for
-// 16 and 32 columns and has no per-row factor: a request for it outside that is served by the batched kernel).
-int sparse_rows_sum_variant(int b, bool rowscale, bool short_lists, double avg_len)
-{
-   // measured (scripts/ab_gather.sh, cfg3): the batched kernel takes 0.3 ms off the K3 gather (short lists per sample),
-   // nothing off the K2 one and costs it 6-50 us at the small sizes -- so K3 takes the batched kernel, K2 the plain one.
-   // Both sit at ~7 TB/s out of the Infinity Cache; with the gathered matrix resident in L2 the same kernel reaches 9.4 TB/s
-   // (scripts/gather_l2_probe.py), which is all an L2-blocked gather order could win.
-   static const int forced = FPCA_TEST_ENV("FPCA_GATHER") ? atoi(FPCA_TEST_ENV("FPCA_GATHER")) : 0; // 1 / 2 force one kernel (A/B)
-   // 3: several rows per wave, for lists of a dozen entries (measured on the 1/8 shard of cfg3, 12.5 entries per sample: see DESIGN 3c)
-   const int variant = forced ? forced : (avg_len > 0 && avg_len <= 24.0 && b <= 32 && !rowscale) ? 3 : ((rowscale || short_lists) ? 2 : 1);
-   if (variant == 3 && b <= 32 && !rowscale) return 3;
-   return variant == 1 ? 1 : 2;
-}
-
-template <class VT>
-static void sparse_rows_sum_t(const uint32_t *ptr, const uint32_t *idx, const VT *V, const double *rowscale, int b, uint64_t nrec,
-                              uint64_t rows_out, double *out, hipStream_t stream, const double *init, bool short_lists, const double *colw, double avg_len)
-{
-   if (!rows_out) return;
-   const unsigned blocks = (unsigned)std::min<uint64_t>(65536, (rows_out + 3) / 4);
-   const int variant = sparse_rows_sum_variant(b, rowscale != nullptr, short_lists, avg_len);
-#define FPCA_GATHER_CASE(B_)                                                                                                    \
-   case B_:                                                                                                                     \
-      if (variant == 3 && B_ <= 32) {                                                                                           \
-         const unsigned blocks3 = (unsigned)std::min<uint64_t>(65536, (rows_out + 4 * (64 / B_) - 1) / (4 * (64 / B_)));        \
-         hipLaunchKernelGGL((k_sparse_rows_sum_short<(B_ <= 32 ? B_ : 32), VT>), dim3(blocks3), dim3(256), 0, stream, ptr, idx, V, nrec, rows_out, out, init, colw); \
-      } else if (variant == 1)                                                                                                  \
-         hipLaunchKernelGGL((k_sparse_rows_sum<B_, VT>), dim3(blocks), dim3(256), 0, stream, ptr, idx, V, rowscale, nrec, rows_out, out, init, colw); \
-      else                                                                                                                      \
-         hipLaunchKernelGGL((k_sparse_rows_sum_batched<B_, VT>), dim3(blocks), dim3(256), 0, stream, ptr, idx, V, rowscale, nrec, rows_out, out, init, colw); \
-      break;
-   switch (b) {
-      FPCA_GATHER_CASE(16)
-      FPCA_GATHER_CASE(32)
-      FPCA_GATHER_CASE(64)
-   default: throw Error(-1, "sparse_rows_sum: block width must be 16, 32 or 64");
-   }
-#undef FPCA_GATHER_CASE
-   HIP_CHECK_LAUNCH();
-}
-void sparse_rows_sum(const uint32_t *ptr, const uint32_t *idx, const double *V, const double *rowscale, int b, uint64_t nrec,
-                     uint64_t rows_out, double *out, hipStream_t stream, const double *init, bool short_lists, double avg_len)
-{
-   sparse_rows_sum_t<double>(ptr, idx, V, rowscale, b, nrec, rows_out, out, stream, init, short_lists, nullptr, avg_len);
-}
-void sparse_rows_sum_f32(const uint32_t *ptr, const uint32_t *idx, const float *V, const double *colw, int b, uint64_t nrec, uint64_t rows_out,
-                         double *out, hipStream_t stream, const double *init, bool short_lists, double avg_len)
-{
-   sparse_rows_sum_t<float>(ptr, idx, V, nullptr, b, nrec, rows_out, out, stream, init, short_lists, colw, avg_len);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Helpers of the hybrid missing-indicator route (device_ctx.hip ensure_hybrid): the few SNPs whose missing calls are too many
-// for the sparse gathers get their indicator matrix E on the matrix cores, as a compacted sub-matrix.
-//   gather_packed_rows  dst[r] = src[idx[r]] (records of `pitch` bytes), rows r >= nidx filled with 0xff = "dosage 0, not missing"
-//   patch_missing_rows  in the records idx[r] of `packed`: code 01 (missing) -> 11 (dosage 0): G.M is unchanged, E becomes 0 --
-//                       the view of the matrix whose remaining missing calls the sparse lists hold
-//   scatter_packed_rows packed[idx[r]] = src[r]  (puts the original records back)
-//   gather_scaled_rows  dst[r][c] = V[idx[r]][c] * scale[idx[r]], rows >= nidx zero        (fp64, [.][b])
-//   scatter_rows        dst[idx[r]][c] = src[r][c]
-__global__ __launch_bounds__(256) void k_gather_packed_rows(const uint8_t *__restrict__ src, size_t pitch, const uint32_t *__restrict__ idx,
-                                                             uint32_t nidx, uint8_t *__restrict__ dst)
-{
-   const u4 *s = blockIdx.x < nidx ? reinterpret_cast<const u4 *>(src + (size_t)idx[blockIdx.x] * pitch) : nullptr;
-   u4 *d = reinterpret_cast<u4 *>(dst + (size_t)blockIdx.x * pitch);
-   const u4 fill = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
-   for (size_t i = threadIdx.x; i < pitch / 16; i += 256) d[i] = s ? s[i] : fill;
-}
-__global__ __launch_bounds__(256) void k_patch_missing_rows(uint8_t *__restrict__ packed, size_t pitch, const uint32_t *__restrict__ idx)
-{
-   u4 *row = reinterpret_cast<u4 *>(packed + (size_t)idx[blockIdx.x] * pitch);
-   for (size_t i = threadIdx.x; i < pitch / 16; i += 256) {
-      u4 x = row[i];
-#pragma unroll
-      for (int k = 0; k < 4; k++) x[k] |= (x[k] & ~(x[k] >> 1) & 0x55555555u) << 1;
-      row[i] = x;
-   }
-}
-__global__ __launch_bounds__(256) void k_scatter_packed_rows(const uint8_t *__restrict__ src, size_t pitch, const uint32_t *__restrict__ idx,
-                                                              uint8_t *__restrict__ packed)
-{
-   const u4 *s = reinterpret_cast<const u4 *>(src + (size_t)blockIdx.x * pitch);
-   u4 *d = reinterpret_cast<u4 *>(packed + (size_t)idx[blockIdx.x] * pitch);
-   for (size_t i = threadIdx.x; i < pitch / 16; i += 256) d[i] = s[i];
-}
-__global__ __launch_bounds__(256) void k_gather_scaled_rows(const double *__restrict__ V, const double *__restrict__ scale,
-                                                             const uint32_t *__restrict__ idx, uint32_t nidx, uint64_t rows_out, int b,
-                                                             double *__restrict__ dst)
-{
-   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < rows_out * b; i += (uint64_t)gridDim.x * 256) {
-      const uint64_t r = i / b;
-      const int c = (int)(i % b);
-      double v = 0.0;
-      if (r < nidx) {
-         const uint32_t j = idx[r];
-         v = V[(uint64_t)j * b + c] * (scale ? scale[j] : 1.0);
-      }
-      dst[i] = v;
-   }
-}
-__global__ __launch_bounds__(256) void k_scatter_rows(const double *__restrict__ src, const uint32_t *__restrict__ idx, uint32_t nidx, int b,
-                                                       double *__restrict__ dst)
-{
-   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < (uint64_t)nidx * b; i += (uint64_t)gridDim.x * 256) {
-      const uint64_t r = i / b;
-      dst[(uint64_t)idx[r] * b + (i % b)] = src[i];
-   }
-}
-void gather_packed_rows(const uint8_t *src, size_t pitch, const uint32_t *idx, uint32_t nidx, uint32_t rows_out, uint8_t *dst, hipStream_t stream)
-{
-   if (!rows_out) return;
-   hipLaunchKernelGGL(k_gather_packed_rows, dim3(rows_out), dim3(256), 0, stream, src, pitch, idx, nidx, dst);
-   HIP_CHECK_LAUNCH();
-}
-void patch_missing_rows(uint8_t *packed, size_t pitch, const uint32_t *idx, uint32_t nidx, hipStream_t stream)
-{
-   if (!nidx) return;
-   hipLaunchKernelGGL(k_patch_missing_rows, dim3(nidx), dim3(256), 0, stream, packed, pitch, idx);
-   HIP_CHECK_LAUNCH();
-}
-void scatter_packed_rows(const uint8_t *src, size_t pitch, const uint32_t *idx, uint32_t nidx, uint8_t *packed, hipStream_t stream)
-{
-   if (!nidx) return;
-   hipLaunchKernelGGL(k_scatter_packed_rows, dim3(nidx), dim3(256), 0, stream, src, pitch, idx, packed);
-   HIP_CHECK_LAUNCH();
-}
-void gather_scaled_rows(const double *V, const double *scale, const uint32_t *idx, uint32_t nidx, uint64_t rows_out, int b, double *dst,
-                        hipStream_t stream)
-{
-   if (!rows_out) return;
-   const unsigned blocks = (unsigned)std::min<uint64_t>(4096, (rows_out * b + 255) / 256);
-   hipLaunchKernelGGL(k_gather_scaled_rows, dim3(blocks), dim3(256), 0, stream, V, scale, idx, nidx, rows_out, b, dst);
-   HIP_CHECK_LAUNCH();
-}
-void scatter_rows(const double *src, const uint32_t *idx, uint32_t nidx, int b, double *dst, hipStream_t stream)
-{
-   if (!nidx) return;
-   const unsigned blocks = (unsigned)std::min<uint64_t>(4096, ((uint64_t)nidx * b + 255) / 256);
-   hipLaunchKernelGGL(k_scatter_rows, dim3(blocks), dim3(256), 0, stream, src, idx, nidx, b, dst);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1863,7 +1508,7 @@ void transpose_packed(const uint8_t *in, size_t pitch_in, uint64_t N_pad, uint64
       hipLaunchKernelGGL(k_transpose_packed<true>, grid, dim3(256), 0, stream, in, pitch_in, out, pitch_out);
    else
       hipLaunchKernelGGL(k_transpose_packed<false>, grid, dim3(256), 0, stream, in, pitch_in, out, pitch_out);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 // the band-tiled arrangement of row-major records (the copy K2 streams): a thread moves the four 16-byte pieces of one (row, chunk);
@@ -1883,7 +1528,7 @@ void tile_packed(const uint8_t *in, size_t pitch, uint64_t rows, uint8_t *out, h
    if (rows % 256 || pitch % 64) throw Error(-1, "tile_packed: rows in multiples of 256, whole 64-byte chunks per row");
    if (!rows) return;
    hipLaunchKernelGGL(k_tile_packed, dim3((unsigned)(pitch / 64), (unsigned)(rows / 256)), dim3(256), 0, stream, in, pitch, out);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 // diagnostic: C(32x32) = A(32x32 int8) * B(32x32 int8)^T-style product through v_mfma_i32_32x32x32_i8 with the operand
@@ -1902,7 +1547,7 @@ __global__ void k_mfma_i8_probe(const int8_t *A /*[32][32] row-major: A[i][k]*/,
 void mfma_i8_probe(const int8_t *A, const int8_t *Bt, int *D, hipStream_t stream)
 {
    hipLaunchKernelGGL(k_mfma_i8_probe, dim3(1), dim3(64), 0, stream, A, Bt, D);
-   HIP_CHECK_LAUNCH();
+   launch_check();
 }
 
 // issue-rate ceiling of v_mfma_i32_32x32x32_i8: 8 independent accumulators per wave, explicit registers (the compiler

@@ -20,6 +20,7 @@
 #include <queue>
 
 #include "ctx.hpp"
+#include "launch_check.hpp"
 #include "ld_planes.hpp"
 
 using namespace fpca;
@@ -93,12 +94,6 @@ __global__ __launch_bounds__(256, 2) void k_king(const uint8_t *__restrict__ pac
          }
       }
    }
-}
-
-void launch_check()
-{
-   const hipError_t e = hipGetLastError();
-   if (e != hipSuccess) throw Error(FPCA_EHIP, std::string("kernel launch failed: ") + hipGetErrorString(e));
 }
 
 // what every entry point refuses (before any device work)

@@ -23,6 +23,7 @@
 #include <cmath>
 
 #include "ctx.hpp"
+#include "launch_check.hpp"
 #include "ld_planes.hpp"
 
 using namespace fpca;
@@ -123,12 +124,6 @@ __global__ __launch_bounds__(256, 2) void k_ld_band(const uint8_t *__restrict__ 
 }
 
 uint32_t ld_nj(uint32_t span) { return (uint32_t)(((uint64_t)span + LD_TILE - 1) / LD_TILE + 1); } // J tiles a tile I can reach
-
-void launch_check()
-{
-   const hipError_t e = hipGetLastError();
-   if (e != hipSuccess) throw Error(FPCA_EHIP, std::string("kernel launch failed: ") + hipGetErrorString(e));
-}
 
 // what both entry points refuse (before any device work)
 void ld_refuse(const fpca_ctx *c, const char *fn, bool needs_maf)

@@ -17,6 +17,7 @@
 #include <cmath>
 
 #include "ctx.hpp"
+#include "launch_check.hpp"
 
 using namespace fpca;
 
@@ -98,8 +99,7 @@ void gather_records(const uint8_t *src, size_t pitch, const uint32_t *idx, uint6
    const uint64_t total = nrec * vpr;
    hipLaunchKernelGGL(k_gather_records, dim3((unsigned)((total + GATHER_TILE - 1) / GATHER_TILE)), dim3(256), 0, stream, src, idx, vpr, total,
                       reinterpret_cast<uint4 *>(dst));
-   const hipError_t e = hipGetLastError();
-   if (e != hipSuccess) throw Error(FPCA_EHIP, std::string("kernel launch failed: ") + hipGetErrorString(e));
+   launch_check();
 }
 } // namespace kern
 

@@ -1,4 +1,4 @@
-"""The missing-call index lists and gather kernels of the exact-integer mode (csrc/kernels_i8.hip: k_count_missing, k_fill_missing,
+"""The missing-call index lists and gather kernels of the exact-integer mode (csrc/missing_kernels.hip: k_count_missing, k_fill_missing,
 k_sparse_rows_sum, k_sparse_rows_sum_batched, k_sparse_rows_sum_short; dispatch in csrc/missing_routes.hip) at the shapes where they can
 go wrong, every comparison exact or with a derived bound.
 

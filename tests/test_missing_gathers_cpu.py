@@ -1,7 +1,7 @@
 """The host-side decisions behind the missing-call list routes of the exact-integer mode, ported to Python, and the test
 matrices of tests/test_gpu_missing_gathers.py.  No device.
 
- * gather_variant: which gather kernel kern::sparse_rows_sum / sparse_rows_sum_f32 launch (csrc/kernels_i8.hip sparse_rows_sum_variant):
+ * gather_variant: which gather kernel kern::sparse_rows_sum / sparse_rows_sum_f32 launch (csrc/missing_kernels.hip sparse_rows_sum_variant):
    1 = k_sparse_rows_sum, 2 = k_sparse_rows_sum_batched, 3 = k_sparse_rows_sum_short.  K2 calls with (short_lists, avg_len) = (False, 0),
    K3 with (True, listed calls per sample); FPCA_GATHER (test build) forces a kernel.  Checked against a table.
  * hybrid_classify: the cost model that decides per SNP whether its missing calls are listed or go to the matrix cores, and whether the
