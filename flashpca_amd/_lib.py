@@ -176,6 +176,8 @@ SIGNATURES = {
     "fpca_bench_ld": (_I, [_P, C.c_uint32, _I, _P, C.POINTER(_D)]),
     "fpca_debug_king_rule": (_I, [_P, _P, _U64, _U64, _P, C.POINTER(_U64)]),
     "fpca_bench_king": (_I, [_P, _I, _P, C.POINTER(_D)]),
+    "fpca_debug_scratch_live": (_I, [C.POINTER(_U64)]),
+    "fpca_debug_scratch_fail_at": (_I, [_U64]),
 }
 
 ABI_VERSION = 4  # FPCA_ABI_VERSION of the include/fpca.h the structures above mirror

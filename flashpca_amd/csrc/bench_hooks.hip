@@ -19,32 +19,29 @@ int fpca_bench_apply(fpca_ctx *ctx, int b, int steps, int warmup, fpca_bench_res
       if (b != 16 && b != 32 && b != 48 && b != 64) throw Error(FPCA_EINVAL, "b must be 16, 32, 48 or 64");
       HIP_CHECK(hipSetDevice(ctx->device));
       ensure_stats(ctx);
-      double *dB = nullptr, *dY = nullptr;
-      HIP_CHECK(hipMalloc(&dB, (size_t)ctx->N_pad * b * sizeof(double)));
-      HIP_CHECK(hipMalloc(&dY, (size_t)ctx->N_pad * b * sizeof(double)));
-      kern::fill_random(dB, ctx->N, ctx->N_pad, b, 12345, ctx->stream);
-      std::vector<hipEvent_t> ev((size_t)steps * 8); // per step: stage boundaries [0..3], K2 / K3 GEMM kernel [4,5] / [6,7]
-      for (auto &e : ev) HIP_CHECK(hipEventCreate(&e));
-      for (int i = 0; i < warmup; i++) apply_xxt_dev(ctx, dB, b, dY, ctx->stream, nullptr);
+      static const char *FN = "fpca_bench_apply";
+      DevMem<double> dB((size_t)ctx->N_pad * b, FN, "the input block"), dY((size_t)ctx->N_pad * b, FN, "the output block");
+      kern::fill_random(dB.p, ctx->N, ctx->N_pad, b, 12345, ctx->stream);
+      std::vector<DevEvent> own; // per step: stage boundaries [0..3], K2 / K3 GEMM kernel [4,5] / [6,7]
+      std::vector<hipEvent_t> ev; // (the handles in a row, as apply_xxt_dev takes them)
+      own.reserve((size_t)steps * 8);
+      for (size_t i = 0; i < (size_t)steps * 8; i++) {
+         own.emplace_back(FN);
+         ev.push_back(own.back());
+      }
+      for (int i = 0; i < warmup; i++) apply_xxt_dev(ctx, dB.p, b, dY.p, ctx->stream, nullptr);
       HIP_CHECK(hipStreamSynchronize(ctx->stream));
-      for (int i = 0; i < steps; i++) apply_xxt_dev(ctx, dB, b, dY, ctx->stream, &ev[(size_t)i * 8]);
+      for (int i = 0; i < steps; i++) apply_xxt_dev(ctx, dB.p, b, dY.p, ctx->stream, &ev[(size_t)i * 8]);
       HIP_CHECK(hipStreamSynchronize(ctx->stream));
       double t2 = 0, t3 = 0, ta = 0, g2 = 0, g3 = 0;
-      float ms = 0;
       for (int i = 0; i < steps; i++) {
-         HIP_CHECK(hipEventElapsedTime(&ms, ev[i * 8 + 0], ev[i * 8 + 1]));
-         t2 += ms;
-         HIP_CHECK(hipEventElapsedTime(&ms, ev[i * 8 + 1], ev[i * 8 + 2]));
-         t3 += ms;
-         HIP_CHECK(hipEventElapsedTime(&ms, ev[i * 8 + 2], ev[i * 8 + 3]));
-         ta += ms;
-         HIP_CHECK(hipEventElapsedTime(&ms, ev[i * 8 + 4], ev[i * 8 + 5]));
-         g2 += ms;
-         HIP_CHECK(hipEventElapsedTime(&ms, ev[i * 8 + 6], ev[i * 8 + 7]));
-         g3 += ms;
+         t2 += elapsed_ms(ev[i * 8 + 0], ev[i * 8 + 1]);
+         t3 += elapsed_ms(ev[i * 8 + 1], ev[i * 8 + 2]);
+         ta += elapsed_ms(ev[i * 8 + 2], ev[i * 8 + 3]);
+         g2 += elapsed_ms(ev[i * 8 + 4], ev[i * 8 + 5]);
+         g3 += elapsed_ms(ev[i * 8 + 6], ev[i * 8 + 7]);
       }
-      HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[(size_t)(steps - 1) * 8 + 3]));
-      res->ms_total = ms;
+      res->ms_total = elapsed_ms(ev[0], ev[(size_t)(steps - 1) * 8 + 3]);
       res->ms_xt = t2 / steps;
       res->ms_x = t3 / steps;
       res->ms_allreduce = ta / steps;
@@ -52,9 +49,6 @@ int fpca_bench_apply(fpca_ctx *ctx, int b, int steps, int warmup, fpca_bench_res
       res->ms_gemm_x = g3 / steps;
       res->flops_per_step = 4.0 * (double)ctx->N * (double)ctx->P_g * b;
       res->packed_bytes_per_step = 2.0 * (double)ctx->np * (double)ctx->P_g;
-      for (auto &e : ev) (void)hipEventDestroy(e);
-      (void)hipFree(dB);
-      (void)hipFree(dY);
    });
 }
 
@@ -127,21 +121,11 @@ int fpca_bench_stats(fpca_ctx *ctx, int reps, double *ms_per_launch, double *byt
    return guarded([&] {
       if (!ctx || reps < 1) throw Error(FPCA_EINVAL, "bad argument to fpca_bench_stats");
       HIP_CHECK(hipSetDevice(ctx->device));
-      hipEvent_t e0, e1;
-      HIP_CHECK(hipEventCreate(&e0));
-      HIP_CHECK(hipEventCreate(&e1));
-      kern::bed_stats(ctx->d_packed, ctx->pitch, ctx->N, ctx->P_g, ctx->stand, ctx->d_lut, ctx->d_mean, ctx->d_sd, ctx->d_sumsq, nullptr, ctx->stream);
-      HIP_CHECK(hipEventRecord(e0, ctx->stream));
-      for (int i = 0; i < reps; i++)
+      const float ms = time_launches(ctx->stream, "fpca_bench_stats", 1, reps, [&] {
          kern::bed_stats(ctx->d_packed, ctx->pitch, ctx->N, ctx->P_g, ctx->stand, ctx->d_lut, ctx->d_mean, ctx->d_sd, ctx->d_sumsq, nullptr, ctx->stream);
-      HIP_CHECK(hipEventRecord(e1, ctx->stream));
-      HIP_CHECK(hipEventSynchronize(e1));
-      float ms = 0;
-      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-      if (ms_per_launch) *ms_per_launch = ms / reps;
+      });
+      if (ms_per_launch) *ms_per_launch = ms;
       if (bytes_per_launch) *bytes_per_launch = (double)ctx->np * (double)ctx->P_g;
-      (void)hipEventDestroy(e0);
-      (void)hipEventDestroy(e1);
    });
 }
 
@@ -158,71 +142,46 @@ int fpca_debug_snp_qc_rule(const double *mean, const uint32_t *n_missing, uint64
 
 int fpca_debug_snp_subset_bench(fpca_ctx *src, const uint8_t *keep, int reps, double *ms_per_launch, double *bytes_per_launch)
 {
-   uint8_t *d_dst = nullptr;
-   uint32_t *d_idx = nullptr;
-   hipEvent_t e0 = nullptr, e1 = nullptr;
-   const int rc = guarded([&] {
+   return guarded([&] {
+      static const char *FN = "fpca_debug_snp_subset_bench";
       if (!src || !keep || reps < 1 || src->dense) throw Error(FPCA_EINVAL, "bad argument to fpca_debug_snp_subset_bench");
       const std::vector<uint32_t> idx = kept_indices(keep, src->P_g);
       if (idx.empty()) throw Error(FPCA_EINVAL, "fpca_debug_snp_subset_bench: the mask keeps no SNP");
       HIP_CHECK(hipSetDevice(src->device));
-      HIP_ALLOC(hipMalloc(&d_dst, src->pitch * idx.size()));
-      HIP_ALLOC(hipMalloc(&d_idx, idx.size() * sizeof(uint32_t)));
-      HIP_CHECK(hipMemcpy(d_idx, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-      HIP_CHECK(hipEventCreate(&e0));
-      HIP_CHECK(hipEventCreate(&e1));
-      kern::gather_records(src->d_packed, src->pitch, d_idx, idx.size(), d_dst, src->stream);
-      HIP_CHECK(hipEventRecord(e0, src->stream));
-      for (int i = 0; i < reps; i++) kern::gather_records(src->d_packed, src->pitch, d_idx, idx.size(), d_dst, src->stream);
-      HIP_CHECK(hipEventRecord(e1, src->stream));
-      HIP_CHECK(hipEventSynchronize(e1));
-      float ms = 0;
-      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-      if (ms_per_launch) *ms_per_launch = ms / reps;
+      DevMem<uint8_t> d_dst(src->pitch * idx.size(), FN, "the compacted records");
+      DevMem<uint32_t> d_idx(idx.size(), FN, "the list of the kept SNPs");
+      HIP_CHECK(hipMemcpy(d_idx.p, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+      const float ms = time_launches(src->stream, FN, 1, reps, [&] { kern::gather_records(src->d_packed, src->pitch, d_idx.p, idx.size(), d_dst.p, src->stream); });
+      if (ms_per_launch) *ms_per_launch = ms;
       if (bytes_per_launch) *bytes_per_launch = 2.0 * (double)src->pitch * (double)idx.size();
    });
-   if (e0) (void)hipEventDestroy(e0);
-   if (e1) (void)hipEventDestroy(e1);
-   if (d_dst) (void)hipFree(d_dst);
-   if (d_idx) (void)hipFree(d_idx);
-   return rc;
 }
 
 // diagnostic used by tests/test_gpu_kernels.py: D = A(16x4) B(4x16) through the MFMA operand mapping of kernels.hip
 int fpca_debug_mfma_probe(const double *A, const double *B, double *D)
 {
    return guarded([&] {
-      double *dA, *dB, *dD;
-      HIP_CHECK(hipMalloc(&dA, 64 * sizeof(double)));
-      HIP_CHECK(hipMalloc(&dB, 64 * sizeof(double)));
-      HIP_CHECK(hipMalloc(&dD, 256 * sizeof(double)));
-      HIP_CHECK(hipMemcpy(dA, A, 64 * sizeof(double), hipMemcpyHostToDevice));
-      HIP_CHECK(hipMemcpy(dB, B, 64 * sizeof(double), hipMemcpyHostToDevice));
-      kern::mfma_layout_probe(dA, dB, dD, nullptr);
+      static const char *FN = "fpca_debug_mfma_probe";
+      DevMem<double> dA(64, FN, "A"), dB(64, FN, "B"), dD(256, FN, "D");
+      HIP_CHECK(hipMemcpy(dA.p, A, 64 * sizeof(double), hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(dB.p, B, 64 * sizeof(double), hipMemcpyHostToDevice));
+      kern::mfma_layout_probe(dA.p, dB.p, dD.p, nullptr);
       HIP_CHECK(hipDeviceSynchronize());
-      HIP_CHECK(hipMemcpy(D, dD, 256 * sizeof(double), hipMemcpyDeviceToHost));
-      (void)hipFree(dA);
-      (void)hipFree(dB);
-      (void)hipFree(dD);
+      HIP_CHECK(hipMemcpy(D, dD.p, 256 * sizeof(double), hipMemcpyDeviceToHost));
    });
 }
 
 int fpca_debug_mfma_i8_probe(const int8_t *A, const int8_t *Bt, int32_t *D)
 {
    return guarded([&] {
-      int8_t *dA, *dB;
-      int *dD;
-      HIP_CHECK(hipMalloc(&dA, 1024));
-      HIP_CHECK(hipMalloc(&dB, 1024));
-      HIP_CHECK(hipMalloc(&dD, 1024 * sizeof(int)));
-      HIP_CHECK(hipMemcpy(dA, A, 1024, hipMemcpyHostToDevice));
-      HIP_CHECK(hipMemcpy(dB, Bt, 1024, hipMemcpyHostToDevice));
-      kern::mfma_i8_probe(dA, dB, dD, nullptr);
+      static const char *FN = "fpca_debug_mfma_i8_probe";
+      DevMem<int8_t> dA(1024, FN, "A"), dB(1024, FN, "Bt");
+      DevMem<int> dD(1024, FN, "D");
+      HIP_CHECK(hipMemcpy(dA.p, A, 1024, hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(dB.p, Bt, 1024, hipMemcpyHostToDevice));
+      kern::mfma_i8_probe(dA.p, dB.p, dD.p, nullptr);
       HIP_CHECK(hipDeviceSynchronize());
-      HIP_CHECK(hipMemcpy(D, dD, 1024 * sizeof(int), hipMemcpyDeviceToHost));
-      (void)hipFree(dA);
-      (void)hipFree(dB);
-      (void)hipFree(dD);
+      HIP_CHECK(hipMemcpy(D, dD.p, 1024 * sizeof(int), hipMemcpyDeviceToHost));
    });
 }
 
@@ -334,47 +293,24 @@ int fpca_debug_k4_fused_bench(fpca_ctx *ctx, int b, int nq, int reps, double *ms
       const uint64_t rows = ctx->N_pad;
       const int planes = kern::update_gram_planes(rows, nq, b);
       if (!planes) throw Error(FPCA_EINVAL, "no fused update + Gram kernel for this shape");
-      std::vector<double *> blk(nq + 1, nullptr);
-      const double **d_ptrs = nullptr;
-      double *d_C = nullptr, *d_part = nullptr;
-      hipEvent_t e[2] = {nullptr, nullptr};
-      auto cleanup = [&] {
-         for (double *p : blk)
-            if (p) (void)hipFree(p);
-         if (d_ptrs) (void)hipFree(d_ptrs);
-         if (d_C) (void)hipFree(d_C);
-         if (d_part) (void)hipFree(d_part);
-         for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-      };
-      try {
-         hipStream_t s = ctx->stream;
-         for (int q = 0; q < nq + 1; q++) {
-            HIP_CHECK(hipMalloc(&blk[q], rows * b * sizeof(double)));
-            kern::fill_random(blk[q], ctx->N, rows, b, 100 + q, s);
-         }
-         HIP_CHECK(hipMalloc(&d_ptrs, (nq + 1) * sizeof(double *)));
-         HIP_CHECK(hipMemcpyAsync(d_ptrs, blk.data(), (nq + 1) * sizeof(double *), hipMemcpyHostToDevice, s));
-         const size_t cnt = (size_t)nq * b * b, cntg = (size_t)(nq + 1) * b * b;
-         HIP_CHECK(hipMalloc(&d_C, cnt * sizeof(double)));
-         HIP_CHECK(hipMalloc(&d_part, cntg * (planes + 1) * sizeof(double)));
-         HIP_CHECK(hipMemsetAsync(d_C, 0, cnt * sizeof(double), s)); // (zero coefficients: the block stays bounded over the repetitions)
-         for (hipEvent_t &x : e) HIP_CHECK(hipEventCreate(&x));
-         for (int r = -2; r < reps; r++) {
-            if (r == 0) HIP_CHECK(hipEventRecord(e[0], s));
-            kern::update_gram(d_ptrs, nq, d_C, blk[nq], blk[nq], rows, b, d_part + cntg, s);
-            kern::reduce_sum(d_part + cntg, d_part, cntg, planes, s);
-         }
-         HIP_CHECK(hipEventRecord(e[1], s));
-         HIP_CHECK(hipEventSynchronize(e[1]));
-         float ms = 0;
-         HIP_CHECK(hipEventElapsedTime(&ms, e[0], e[1]));
-         *ms_fused = ms / reps;
-      } catch (...) {
-         cleanup();
-         throw;
+      static const char *FN = "fpca_debug_k4_fused_bench";
+      hipStream_t s = ctx->stream;
+      std::vector<DevMem<double>> own;
+      std::vector<double *> blk; // (the pointers in a row, as the kernels take them)
+      for (int q = 0; q < nq + 1; q++) {
+         own.emplace_back(rows * b, FN, "a basis block");
+         blk.push_back(own.back().p);
+         kern::fill_random(blk[q], ctx->N, rows, b, 100 + q, s);
       }
-      cleanup();
+      DevMem<const double *> d_ptrs(nq + 1, FN, "the block pointers");
+      HIP_CHECK(hipMemcpyAsync(d_ptrs.p, blk.data(), (nq + 1) * sizeof(double *), hipMemcpyHostToDevice, s));
+      const size_t cnt = (size_t)nq * b * b, cntg = (size_t)(nq + 1) * b * b;
+      DevMem<double> d_C(cnt, FN, "the coefficients"), d_part(cntg * (planes + 1), FN, "the partial planes");
+      HIP_CHECK(hipMemsetAsync(d_C.p, 0, cnt * sizeof(double), s)); // (zero coefficients: the block stays bounded over the repetitions)
+      *ms_fused = time_launches(s, FN, 2, reps, [&] {
+         kern::update_gram(d_ptrs.p, nq, d_C.p, blk[nq], blk[nq], rows, b, d_part.p + cntg, s);
+         kern::reduce_sum(d_part.p + cntg, d_part.p, cntg, planes, s);
+      });
    });
 }
 
@@ -384,59 +320,38 @@ int fpca_debug_k4_bench(fpca_ctx *ctx, int b, int nq, int reps, double *ms_gram,
       if (!ctx || nq < 1 || nq > 64 || reps < 1 || (b != 16 && b != 32 && b != 48 && b != 64)) throw Error(FPCA_EINVAL, "bad argument to fpca_debug_k4_bench");
       HIP_CHECK(hipSetDevice(ctx->device));
       const uint64_t rows = ctx->N_pad;
-      std::vector<double *> blk(nq + 2, nullptr);
-      const double **d_ptrs = nullptr;
-      double *d_C = nullptr, *d_part = nullptr, *d_G = nullptr;
-      hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-      auto cleanup = [&] {
-         for (double *p : blk)
-            if (p) (void)hipFree(p);
-         if (d_ptrs) (void)hipFree(d_ptrs);
-         if (d_C) (void)hipFree(d_C);
-         if (d_part) (void)hipFree(d_part);
-         if (d_G) (void)hipFree(d_G);
-         for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-      };
-      try {
-         hipStream_t s = ctx->stream;
-         for (int q = 0; q < nq + 2; q++) {
-            HIP_CHECK(hipMalloc(&blk[q], rows * b * sizeof(double)));
-            kern::fill_random(blk[q], ctx->N, rows, b, 100 + q, s);
-         }
-         HIP_CHECK(hipMalloc(&d_ptrs, (nq + 2) * sizeof(double *)));
-         HIP_CHECK(hipMemcpyAsync(d_ptrs, blk.data(), (nq + 2) * sizeof(double *), hipMemcpyHostToDevice, s));
-         const size_t cnt = (size_t)nq * b * b;
-         const int grows = kern::gram_rows(rows, nq, b), ns = kern::gram_splits(rows, grows) * 4;
-         HIP_CHECK(hipMalloc(&d_C, cnt * sizeof(double)));
-         HIP_CHECK(hipMalloc(&d_G, cnt * sizeof(double)));
-         HIP_CHECK(hipMalloc(&d_part, cnt * ns * sizeof(double)));
-         kern::fill_random(d_C, cnt / b, cnt / b, b, 7, s);
-         for (hipEvent_t &x : e) HIP_CHECK(hipEventCreate(&x));
-         for (int w = 0; w < 2; w++) { // warm-up
-            kern::gram(d_ptrs, nq, blk[nq], d_part, rows, b, grows, s);
-            kern::reduce_sum(d_part, d_G, cnt, ns, s);
-            kern::block_gemm(d_ptrs, nq, d_C, blk[nq], blk[nq + 1], rows, b, s);
-         }
-         HIP_CHECK(hipEventRecord(e[0], s));
-         for (int r = 0; r < reps; r++) {
-            kern::gram(d_ptrs, nq, blk[nq], d_part, rows, b, grows, s);
-            kern::reduce_sum(d_part, d_G, cnt, ns, s);
-         }
-         HIP_CHECK(hipEventRecord(e[1], s));
-         for (int r = 0; r < reps; r++) kern::block_gemm(d_ptrs, nq, d_C, blk[nq], blk[nq + 1], rows, b, s);
-         HIP_CHECK(hipEventRecord(e[2], s));
-         HIP_CHECK(hipEventSynchronize(e[2]));
-         float ms = 0;
-         HIP_CHECK(hipEventElapsedTime(&ms, e[0], e[1]));
-         if (ms_gram) *ms_gram = ms / reps;
-         HIP_CHECK(hipEventElapsedTime(&ms, e[1], e[2]));
-         if (ms_gemm) *ms_gemm = ms / reps;
-      } catch (...) {
-         cleanup();
-         throw;
+      static const char *FN = "fpca_debug_k4_bench";
+      hipStream_t s = ctx->stream;
+      std::vector<DevMem<double>> own;
+      std::vector<double *> blk; // (the pointers in a row, as the kernels take them)
+      for (int q = 0; q < nq + 2; q++) {
+         own.emplace_back(rows * b, FN, "a basis block");
+         blk.push_back(own.back().p);
+         kern::fill_random(blk[q], ctx->N, rows, b, 100 + q, s);
       }
-      cleanup();
+      DevMem<const double *> d_ptrs(nq + 2, FN, "the block pointers");
+      HIP_CHECK(hipMemcpyAsync(d_ptrs.p, blk.data(), (nq + 2) * sizeof(double *), hipMemcpyHostToDevice, s));
+      const size_t cnt = (size_t)nq * b * b;
+      const int grows = kern::gram_rows(rows, nq, b), ns = kern::gram_splits(rows, grows) * 4;
+      DevMem<double> d_C(cnt, FN, "the coefficients"), d_G(cnt, FN, "the Gram matrices"), d_part(cnt * ns, FN, "the partial planes");
+      kern::fill_random(d_C.p, cnt / b, cnt / b, b, 7, s);
+      DevEvent e0(FN), e1(FN), e2(FN);
+      for (int w = 0; w < 2; w++) { // warm-up
+         kern::gram(d_ptrs.p, nq, blk[nq], d_part.p, rows, b, grows, s);
+         kern::reduce_sum(d_part.p, d_G.p, cnt, ns, s);
+         kern::block_gemm(d_ptrs.p, nq, d_C.p, blk[nq], blk[nq + 1], rows, b, s);
+      }
+      HIP_CHECK(hipEventRecord(e0, s));
+      for (int r = 0; r < reps; r++) {
+         kern::gram(d_ptrs.p, nq, blk[nq], d_part.p, rows, b, grows, s);
+         kern::reduce_sum(d_part.p, d_G.p, cnt, ns, s);
+      }
+      HIP_CHECK(hipEventRecord(e1, s));
+      for (int r = 0; r < reps; r++) kern::block_gemm(d_ptrs.p, nq, d_C.p, blk[nq], blk[nq + 1], rows, b, s);
+      HIP_CHECK(hipEventRecord(e2, s));
+      HIP_CHECK(hipEventSynchronize(e2));
+      if (ms_gram) *ms_gram = elapsed_ms(e0, e1) / reps;
+      if (ms_gemm) *ms_gemm = elapsed_ms(e1, e2) / reps;
    });
 }
 
@@ -495,15 +410,13 @@ int fpca_debug_missing_lists(fpca_ctx *ctx, int b, int by_sample, uint32_t *ptr_
 int fpca_debug_gather(int b, int use_f32, const uint32_t *ptr, const uint32_t *idx, uint64_t nnz, const void *V, uint64_t v_rows, const double *rowscale,
                       const double *colw, const double *init, uint64_t nrec, uint64_t rows_out, int short_lists, double avg_len, double *out, int *variant)
 {
-   std::vector<void *> dev;
-   auto upload = [&](const void *h, size_t bytes) -> void * {
-      void *d = nullptr;
-      HIP_ALLOC(hipMalloc(&d, std::max<size_t>(bytes, 16)));
-      dev.push_back(d);
-      if (h && bytes) HIP_CHECK(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice));
-      return d;
-   };
-   const int rc = guarded([&] {
+   return guarded([&] {
+      std::vector<DevMem<uint8_t>> dev;
+      auto upload = [&](const void *h, size_t bytes) -> void * { // (at least 16 bytes: the kernels are handed a pointer for an empty array too)
+         dev.emplace_back(bytes, "fpca_debug_gather", "an operand", 16);
+         if (h && bytes) HIP_CHECK(hipMemcpy(dev.back().p, h, bytes, hipMemcpyHostToDevice));
+         return dev.back().p;
+      };
       if ((b != 16 && b != 32 && b != 64) || !ptr || !idx || !V || !out || !variant || v_rows == 0 || v_rows >= (1ull << 32) || rows_out == 0 ||
           nrec > rows_out || rows_out >= (1ull << 31) || nnz >= (1ull << 32))
          throw Error(FPCA_EINVAL, "bad argument to fpca_debug_gather");
@@ -532,8 +445,32 @@ int fpca_debug_gather(int b, int use_f32, const uint32_t *ptr, const uint32_t *i
       HIP_CHECK(hipDeviceSynchronize());
       HIP_CHECK(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));
    });
-   for (void *d : dev) (void)hipFree(d);
-   return rc;
+}
+
+// dev_scratch.hpp's counters and countdown: they exist in the test build only
+int fpca_debug_scratch_live(uint64_t out[3])
+{
+   return guarded([&] {
+#ifdef FPCA_TEST_HOOKS
+      if (!out) throw Error(FPCA_EINVAL, "bad argument to fpca_debug_scratch_live");
+      for (int k = 0; k < 3; k++) out[k] = g_scratch_live[k].load();
+#else
+      (void)out;
+      throw Error(FPCA_EINVAL, "fpca_debug_scratch_live: this is the product build; the counters exist with -DFPCA_TEST_HOOKS only");
+#endif
+   });
+}
+
+int fpca_debug_scratch_fail_at(uint64_t n)
+{
+   return guarded([&] {
+#ifdef FPCA_TEST_HOOKS
+      g_scratch_fail_at.store(n);
+#else
+      (void)n;
+      throw Error(FPCA_EINVAL, "fpca_debug_scratch_fail_at: this is the product build; nothing is injected without -DFPCA_TEST_HOOKS");
+#endif
+   });
 }
 
 int fpca_debug_mfma_peak(int waves_per_simd, int iters, int pattern, double *tflops)

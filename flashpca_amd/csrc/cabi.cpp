@@ -22,6 +22,23 @@ namespace fpca {
 const char *last_error_cstr();
 }
 
+namespace {
+// the shape of every fpca_create*: a fresh context that body(c) fills; *out gets it, or NULL and the context is freed when body throws
+template <typename F> int create_ctx(fpca_ctx **out, F &&body)
+{
+   if (!out) return FPCA_EINVAL;
+   *out = nullptr;
+   fpca_ctx *c = new fpca_ctx();
+   const int rc = guarded([&] { body(c); });
+   if (rc != FPCA_OK) {
+      ctx_free(c);
+      return rc;
+   }
+   *out = c;
+   return FPCA_OK;
+}
+} // namespace
+
 // =====================================================================================================
 extern "C" {
 
@@ -64,22 +81,13 @@ int fpca_device_name(int device, char *buf, int buflen)
 
 int fpca_create(fpca_ctx **out, const uint8_t *packed, uint64_t N, uint64_t P_g, int stand_method, int device, int accum)
 {
-   if (!out) return FPCA_EINVAL;
-   *out = nullptr;
-   fpca_ctx *c = new fpca_ctx();
-   int rc = guarded([&] {
+   return create_ctx(out, [&](fpca_ctx *c) {
       if (!packed && P_g > 0) throw Error(FPCA_EINVAL, "packed is NULL");
       ctx_alloc_common(c, N, P_g, stand_method, device, accum);
       if (P_g > 0)
          HIP_CHECK(hipMemcpy2DAsync(c->d_packed, c->pitch, packed, c->np, c->np, P_g, hipMemcpyHostToDevice, c->stream));
       ctx_finish_upload(c);
    });
-   if (rc != FPCA_OK) {
-      ctx_free(c);
-      return rc;
-   }
-   *out = c;
-   return FPCA_OK;
 }
 
 namespace {
@@ -118,11 +126,8 @@ bool parallel_pread(int fd, uint8_t *buf, uint64_t want, off_t off)
 int fpca_create_from_bed(fpca_ctx **out, const char *bed_path, uint64_t N, uint64_t snp_begin, uint64_t P_g,
                          int stand_method, int device, int accum, uint64_t *P_total)
 {
-   if (!out) return FPCA_EINVAL;
-   *out = nullptr;
-   fpca_ctx *c = new fpca_ctx();
    int fd = -1;
-   int rc = guarded([&] {
+   const int rc = create_ctx(out, [&](fpca_ctx *c) {
       if (N == 0) throw Error(FPCA_EINVAL, "N must be > 0");
       fd = open(bed_path, O_RDONLY);
       if (fd < 0) // data.cpp:156-161
@@ -159,48 +164,38 @@ int fpca_create_from_bed(fpca_ctx **out, const char *bed_path, uint64_t N, uint6
       // two pinned bounce buffers -> 1-D H2D copy into a device staging buffer -> repitch kernel into the resident matrix;
       // the read of chunk i+1 overlaps the copy of chunk i
       const uint64_t rows_per_chunk = std::max<uint64_t>(1, (64ull << 20) / np);
-      uint8_t *bounce[2] = {nullptr, nullptr}, *dstage[2] = {nullptr, nullptr};
-      hipEvent_t done[2] = {nullptr, nullptr};
-      auto cleanup = [&] {
-         for (int i = 0; i < 2; i++) {
-            if (bounce[i]) (void)hipHostFree(bounce[i]);
-            if (dstage[i]) (void)hipFree(dstage[i]);
-            if (done[i]) (void)hipEventDestroy(done[i]);
+      struct Slot {
+         PinnedMem bounce;
+         DevMem<uint8_t> dstage;
+         DevEvent done;
+         explicit Slot(size_t bytes)
+            : bounce(bytes, "fpca_create_from_bed", "a bounce buffer"), dstage(bytes, "fpca_create_from_bed", "a staging buffer"), done("fpca_create_from_bed")
+         {
          }
       };
-      try {
-         int slot = 0;
-         for (uint64_t r0 = 0; r0 < pg; r0 += rows_per_chunk, slot ^= 1) {
-            const uint64_t nr = std::min(rows_per_chunk, pg - r0);
-            if (!bounce[slot]) { // the second slot's 64 MB of pinned memory (14 ms to allocate) come while the first chunk is on the wire
-               HIP_CHECK(hipHostMalloc(&bounce[slot], std::min(rows_per_chunk, pg) * np, hipHostMallocDefault));
-               HIP_CHECK(hipMalloc(&dstage[slot], std::min(rows_per_chunk, pg) * np));
-               HIP_CHECK(hipEventCreate(&done[slot]));
-            }
-            HIP_CHECK(hipEventSynchronize(done[slot])); // the previous copy out of this slot has finished
-            const uint64_t want = nr * np;
-            const off_t off = (off_t)(3 + np * (snp_begin + r0)); // data.cpp:218
-            if (!parallel_pread(fd, bounce[slot], want, off)) throw Error(FPCA_EIO, std::string("short read from ") + bed_path);
-            HIP_CHECK(hipMemcpyAsync(dstage[slot], bounce[slot], want, hipMemcpyHostToDevice, c->stream));
-            kern::repitch(dstage[slot], np, nr, c->d_packed + r0 * c->pitch, c->pitch, c->stream);
-            HIP_CHECK(hipEventRecord(done[slot], c->stream));
-         }
-         HIP_CHECK(hipStreamSynchronize(c->stream));
-      } catch (...) {
-         cleanup();
-         throw;
+      std::vector<Slot> slots;
+      slots.reserve(2);
+      int slot = 0;
+      for (uint64_t r0 = 0; r0 < pg; r0 += rows_per_chunk, slot ^= 1) {
+         const uint64_t nr = std::min(rows_per_chunk, pg - r0);
+         // the second slot's 64 MB of pinned memory (14 ms to allocate) come while the first chunk is on the wire
+         if (slots.size() <= (size_t)slot) slots.emplace_back(std::min(rows_per_chunk, pg) * np);
+         Slot &sl = slots[slot];
+         HIP_CHECK(hipEventSynchronize(sl.done)); // the previous copy out of this slot has finished
+         const uint64_t want = nr * np;
+         const off_t off = (off_t)(3 + np * (snp_begin + r0)); // data.cpp:218
+         if (!parallel_pread(fd, sl.bounce.p, want, off)) throw Error(FPCA_EIO, std::string("short read from ") + bed_path);
+         HIP_CHECK(hipMemcpyAsync(sl.dstage.p, sl.bounce.p, want, hipMemcpyHostToDevice, c->stream));
+         kern::repitch(sl.dstage.p, np, nr, c->d_packed + r0 * c->pitch, c->pitch, c->stream);
+         HIP_CHECK(hipEventRecord(sl.done, c->stream));
       }
-      cleanup();
+      HIP_CHECK(hipStreamSynchronize(c->stream));
+      slots.clear();
       ctx_finish_upload(c);
       lap(".bed -> HBM");
    });
    if (fd >= 0) close(fd);
-   if (rc != FPCA_OK) {
-      ctx_free(c);
-      return rc;
-   }
-   *out = c;
-   return FPCA_OK;
+   return rc;
 }
 
 int fpca_create_synthetic(fpca_ctx **out, uint64_t N, uint64_t snp_begin, uint64_t P_g, uint64_t seed, int n_pop,
@@ -217,10 +212,7 @@ int fpca_create_synthetic(fpca_ctx **out, uint64_t N, uint64_t snp_begin, uint64
 int fpca_create_synthetic_model(fpca_ctx **out, uint64_t N, uint64_t snp_begin, uint64_t P_g, uint64_t seed, const fpca_synth_model *model,
                                 int stand_method, int device, int accum)
 {
-   if (!out) return FPCA_EINVAL;
-   *out = nullptr;
-   fpca_ctx *c = new fpca_ctx();
-   int rc = guarded([&] {
+   return create_ctx(out, [&](fpca_ctx *c) {
       if (!model) throw Error(FPCA_EINVAL, "model is NULL");
       const int n_pop = model->n_pop;
       const double fst = model->fst, missing_rate = model->missing_rate;
@@ -242,20 +234,11 @@ int fpca_create_synthetic_model(fpca_ctx **out, uint64_t N, uint64_t snp_begin, 
                            (uint32_t)std::llround(model->conc_frac * 65536.0), med_q32, sig2_fp);
       HIP_CHECK(hipStreamSynchronize(c->stream));
    });
-   if (rc != FPCA_OK) {
-      ctx_free(c);
-      return rc;
-   }
-   *out = c;
-   return FPCA_OK;
 }
 
 int fpca_create_dense(fpca_ctx **out, const double *X, int64_t ldx, uint64_t N, uint64_t P_g, int stand_method, int device)
 {
-   if (!out) return FPCA_EINVAL;
-   *out = nullptr;
-   fpca_ctx *c = new fpca_ctx();
-   int rc = guarded([&] {
+   return create_ctx(out, [&](fpca_ctx *c) {
       if (!X || ldx < (int64_t)N || P_g == 0) throw Error(FPCA_EINVAL, "bad argument to fpca_create_dense");
       ctx_alloc_common(c, N, P_g, stand_method, device, FPCA_ACCUM_FP64, true);
       // column-major N x P on the host == row-major [P][N] : one strided copy into the padded [P_pad][N_pad] image
@@ -265,21 +248,9 @@ int fpca_create_dense(fpca_ctx **out, const double *X, int64_t ldx, uint64_t N, 
       std::vector<double> ss(P_g);
       HIP_CHECK(hipMemcpyAsync(ss.data(), c->d_sumsq, P_g * sizeof(double), hipMemcpyDeviceToHost, c->stream));
       HIP_CHECK(hipStreamSynchronize(c->stream));
-      double tot = 0;
-      for (size_t i0 = 0; i0 < ss.size(); i0 += 1024) {
-         double sblk = 0;
-         for (size_t i = i0; i < std::min(ss.size(), i0 + 1024); i++) sblk += ss[i];
-         tot += sblk;
-      }
-      c->trace_local = tot; // randompca.cpp:154: sum X^2 of the standardised matrix
+      c->trace_local = blocked_sum(ss.data(), ss.size()); // randompca.cpp:154: sum X^2 of the standardised matrix
       c->stats_done = true;
    });
-   if (rc != FPCA_OK) {
-      ctx_free(c);
-      return rc;
-   }
-   *out = c;
-   return FPCA_OK;
 }
 
 void fpca_destroy(fpca_ctx *ctx) { ctx_free(ctx); }

@@ -2,6 +2,7 @@
 #pragma once
 #include <sched.h>
 
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -26,6 +27,20 @@ constexpr int X_KC = 64;     // K3: SNPs per LDS chunk
 constexpr int MAX_BLOCKVEC = 64; // widest block the kernels are instantiated for (NT <= 4)
 
 inline uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
+
+// Sum of n doubles in blocks of 1024: each block added left to right, the block sums added in order.  Reproducible and accurate enough
+// for a trace; the association order is part of the bits of trace_local and of UCCA's column means, so every caller shares this loop.
+inline double blocked_sum(const double *x, size_t n)
+{
+   double tot = 0;
+   for (size_t i0 = 0; i0 < n; i0 += 1024) {
+      double s = 0;
+      const size_t i1 = n < i0 + 1024 ? n : i0 + 1024;
+      for (size_t i = i0; i < i1; i++) s += x[i];
+      tot += s;
+   }
+   return tot;
+}
 
 // Test and diagnostic switches -- forced missing-indicator modes and split plans, allocation-failure injection, the
 // host-memory test transport and the failure injection of the CLI launcher -- exist only in builds compiled with

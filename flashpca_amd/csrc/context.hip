@@ -167,28 +167,18 @@ void ensure_stats(fpca_ctx *c)
       masked_stats(c);
       return;
    }
-   uint32_t *d_nmiss = nullptr;
+   DevMem<uint32_t> d_nmiss(c->P_g, "ensure_stats", "the per-SNP missing counts");
    std::vector<uint32_t> nm(c->P_g);
-   if (c->P_g) HIP_CHECK(hipMalloc(&d_nmiss, c->P_g * sizeof(uint32_t)));
-   kern::bed_stats(c->d_packed, c->pitch, c->N, c->P_g, c->stand, c->d_lut, c->d_mean, c->d_sd, c->d_sumsq, d_nmiss, c->stream);
+   kern::bed_stats(c->d_packed, c->pitch, c->N, c->P_g, c->stand, c->d_lut, c->d_mean, c->d_sd, c->d_sumsq, d_nmiss.p, c->stream);
    std::vector<double> ss(c->P_g);
    HIP_CHECK(hipMemcpyAsync(ss.data(), c->d_sumsq, c->P_g * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-   if (c->P_g) HIP_CHECK(hipMemcpyAsync(nm.data(), d_nmiss, c->P_g * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+   if (c->P_g) HIP_CHECK(hipMemcpyAsync(nm.data(), d_nmiss.p, c->P_g * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
    HIP_CHECK(hipStreamSynchronize(c->stream));
-   if (d_nmiss) (void)hipFree(d_nmiss);
    c->n_missing = 0;
    for (uint32_t v : nm) c->n_missing += v;
    c->missing_known = true;
    c->h_nmiss.swap(nm);
-   // pairwise-ish (blocked) summation for a reproducible, accurate trace
-   double tot = 0;
-   for (size_t i0 = 0; i0 < ss.size(); i0 += 1024) {
-      double s = 0;
-      const size_t i1 = std::min(ss.size(), i0 + 1024);
-      for (size_t i = i0; i < i1; i++) s += ss[i];
-      tot += s;
-   }
-   c->trace_local = tot;
+   c->trace_local = blocked_sum(ss.data(), ss.size()); // (reproducible and accurate)
    c->stats_done = true;
 }
 

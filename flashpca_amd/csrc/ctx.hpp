@@ -12,6 +12,8 @@
 //   download.hip        pinned, pipelined result download
 //   hip_backend.hip     BlockBackend over HBM-resident blocks (what solver.cpp drives)
 //   bench_hooks.hip     include/fpca_debug.h: measurement hooks and hardware probes
+//   dev_scratch.hpp     owners of the device memory, pinned memory and events of ONE call (DevMem, PinnedMem, DevEvent), dev_alloc and
+//                       the sized out-of-memory report; what lives as long as the context is a member below, freed by ctx_free
 //   ucca.hip            fpca_ucca: per-SNP association with k phenotypes through the K2 pass (+ f_tail.hpp, its F tail)
 //   scca.hip            fpca_scca_prepare / fpca_scca_fit: sparse CCA iterated on the resident P x k matrix C = X'Y (+ scca.hpp)
 //   scca_cv.hip         fpca_scca_cv: K-fold cross-validation of the SCCA penalties, per-fold statistics from one pass over the packed stream
@@ -40,6 +42,7 @@
 #include "../../include/fpca.h"
 #include "backend.hpp"
 #include "common.hpp"
+#include "dev_scratch.hpp"
 #include "kernels.hpp"
 
 namespace fpca {
@@ -67,7 +70,8 @@ struct RcclApi {
 
 RcclApi &rccl();
 
-// allocations whose failure may legitimately be "does not fit": out-of-memory becomes FPCA_ENOMEM, anything else FPCA_EHIP
+// context-lifetime allocations whose failure may legitimately be "does not fit": out-of-memory becomes FPCA_ENOMEM, anything else
+// FPCA_EHIP (the scratch of one call goes through dev_alloc, dev_scratch.hpp)
 #define HIP_ALLOC(expr)                                                                                      \
    do {                                                                                                      \
       hipError_t e__ = (expr);                                                                               \

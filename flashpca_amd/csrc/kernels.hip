@@ -24,6 +24,7 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "dev_scratch.hpp"
 #include "kernels.hpp"
 #include "launch_check.hpp"
 #include "synth.hpp"
@@ -2008,22 +2009,15 @@ __global__ __launch_bounds__(256, 1) void k_mfma_peak(double *out, int iters, in
 
 double mfma_peak_tflops(int waves_per_simd, int iters, int pattern, hipStream_t stream)
 {
-   double *d = nullptr;
-   if (hipMalloc(&d, 8) != hipSuccess) throw Error(-3, "hipMalloc failed");
+   DevMem<double> d(1, "fpca_debug_mfma_peak", "the probe's output word");
    const int blocks = 256 * waves_per_simd; // one 256-thread workgroup = one wave per SIMD of a CU
-   hipEvent_t e0, e1;
-   (void)hipEventCreate(&e0);
-   (void)hipEventCreate(&e1);
-   hipLaunchKernelGGL(k_mfma_peak, dim3(blocks), dim3(256), 0, stream, d, iters / 10, pattern);
+   DevEvent e0("fpca_debug_mfma_peak"), e1("fpca_debug_mfma_peak");
+   hipLaunchKernelGGL(k_mfma_peak, dim3(blocks), dim3(256), 0, stream, d.p, iters / 10, pattern);
    (void)hipEventRecord(e0, stream);
-   hipLaunchKernelGGL(k_mfma_peak, dim3(blocks), dim3(256), 0, stream, d, iters, pattern);
+   hipLaunchKernelGGL(k_mfma_peak, dim3(blocks), dim3(256), 0, stream, d.p, iters, pattern);
    (void)hipEventRecord(e1, stream);
    (void)hipEventSynchronize(e1);
-   float ms = 0;
-   (void)hipEventElapsedTime(&ms, e0, e1);
-   (void)hipEventDestroy(e0);
-   (void)hipEventDestroy(e1);
-   (void)hipFree(d);
+   const float ms = elapsed_ms(e0, e1);
    const double flops = (double)blocks * 4 /*waves*/ * (double)iters * 8 * 2048.0;
    return flops / (ms * 1e-3) / 1e12;
 }

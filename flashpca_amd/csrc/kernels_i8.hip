@@ -25,6 +25,7 @@
 #include <utility>
 
 #include "common.hpp"
+#include "dev_scratch.hpp"
 #include "kernels.hpp"
 #include "launch_check.hpp"
 
@@ -1725,22 +1726,15 @@ __global__ __launch_bounds__(256, 1) void k_mfma_i8_peak(int *out, int iters, ui
 
 double mfma_i8_peak_tops(int waves_per_simd, int iters, uint32_t fill, hipStream_t stream)
 {
-   int *d = nullptr;
-   (void)hipMalloc(&d, 4096);
+   DevMem<int> d(1024, "fpca_debug_mfma_peak", "the probe's output words");
    const int blocks = 256 * waves_per_simd;
-   hipEvent_t e0, e1;
-   (void)hipEventCreate(&e0);
-   (void)hipEventCreate(&e1);
-   hipLaunchKernelGGL(k_mfma_i8_peak, dim3(blocks), dim3(256), 0, stream, d, iters / 10, fill);
+   DevEvent e0("fpca_debug_mfma_peak"), e1("fpca_debug_mfma_peak");
+   hipLaunchKernelGGL(k_mfma_i8_peak, dim3(blocks), dim3(256), 0, stream, d.p, iters / 10, fill);
    (void)hipEventRecord(e0, stream);
-   hipLaunchKernelGGL(k_mfma_i8_peak, dim3(blocks), dim3(256), 0, stream, d, iters, fill);
+   hipLaunchKernelGGL(k_mfma_i8_peak, dim3(blocks), dim3(256), 0, stream, d.p, iters, fill);
    (void)hipEventRecord(e1, stream);
    (void)hipEventSynchronize(e1);
-   float ms = 0;
-   (void)hipEventElapsedTime(&ms, e0, e1);
-   (void)hipEventDestroy(e0);
-   (void)hipEventDestroy(e1);
-   (void)hipFree(d);
+   const float ms = elapsed_ms(e0, e1);
    const double ops = (double)blocks * 4 /*waves*/ * (double)iters * 8 * 65536.0;
    return ops / (ms * 1e-3) / 1e12;
 }

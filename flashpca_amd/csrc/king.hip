@@ -120,64 +120,55 @@ bool king_force_general()
 }
 
 // device buffers of one call
-struct KingScratch {
-   uint8_t *d_smp = nullptr, *d_keep = nullptr; // the sample-major copy [N_pad][pitch]; keep [N]
+struct KingBufs {
+   DevMem<uint8_t> d_smp, d_keep; // the sample-major copy [N_pad][pitch]; keep [N]
    size_t pitch = 0;
    uint32_t npad = 0;
-   uint32_t *d_tot = nullptr, *d_i = nullptr, *d_j = nullptr;
-   double *d_phi = nullptr;
-   unsigned long long *d_count = nullptr;
-   hipEvent_t e0 = nullptr, e1 = nullptr;
-   ~KingScratch()
+   DevMem<uint32_t> d_tot, d_i, d_j;
+   DevMem<double> d_phi;
+   DevMem<unsigned long long> d_count;
+   // the pair list of `slots` entries and its counter
+   void alloc_pairs(size_t slots, const char *fn)
    {
-      for (void *p : {(void *)d_smp, (void *)d_keep, (void *)d_tot, (void *)d_i, (void *)d_j, (void *)d_phi, (void *)d_count})
-         if (p) (void)hipFree(p);
-      if (e0) (void)hipEventDestroy(e0);
-      if (e1) (void)hipEventDestroy(e1);
+      d_i = DevMem<uint32_t>(slots, fn, "the pair list (i)");
+      d_j = DevMem<uint32_t>(slots, fn, "the pair list (j)");
+      d_phi = DevMem<double>(slots, fn, "the pair list (phi)");
+      d_count = DevMem<unsigned long long>(1, fn, "the pair counter");
    }
 };
 
 // the sample-major operand and its per-sample totals, enqueued on the context's stream
-void king_make_operand(fpca_ctx *c, KingScratch &s, const char *fn)
+void king_make_operand(fpca_ctx *c, KingBufs &s, const char *fn)
 {
    s.pitch = (size_t)round_up(c->P_pad / 4, 128);
    s.npad = (uint32_t)(4 * s.pitch - c->P_g);
    const size_t need = (size_t)c->N_pad * s.pitch;
-   const hipError_t e = hipMalloc(&s.d_smp, need);
-   if (e == hipErrorOutOfMemory) {
-      (void)hipGetLastError();
-      size_t fr = 0, tot = 0;
-      (void)hipMemGetInfo(&fr, &tot);
-      const double mb = 1.0 / (1024.0 * 1024.0);
-      char msg[384];
-      std::snprintf(msg, sizeof(msg), "%s: the sample-major copy needs %.1f MiB of device memory (%llu samples x %llu bytes); %.1f of %.1f MiB are free on device %d",
-                    fn, (double)need * mb, (unsigned long long)c->N_pad, (unsigned long long)s.pitch, (double)fr * mb, (double)tot * mb, c->device);
-      throw Error(FPCA_ENOMEM, msg);
-   }
-   if (e != hipSuccess) throw Error(FPCA_EHIP, std::string("hipMalloc of the sample-major copy failed: ") + hipGetErrorString(e));
-   HIP_CHECK(hipMemsetAsync(s.d_smp, PAD_BYTE, need, c->stream));
-   kern::transpose_packed(c->d_packed, c->pitch, c->N_pad, c->P_pad, s.d_smp, s.pitch, c->stream, false);
-   HIP_ALLOC(hipMalloc(&s.d_tot, c->N * 4 * sizeof(uint32_t)));
-   kern::ld_totals(s.d_smp, s.pitch, c->N, s.d_tot, c->stream);
+   char detail[96];
+   std::snprintf(detail, sizeof(detail), "%llu samples x %llu bytes", (unsigned long long)c->N_pad, (unsigned long long)s.pitch);
+   s.d_smp = DevMem<uint8_t>(need, fn, "sample-major copy", 0, detail, c->device);
+   HIP_CHECK(hipMemsetAsync(s.d_smp.p, PAD_BYTE, need, c->stream));
+   kern::transpose_packed(c->d_packed, c->pitch, c->N_pad, c->P_pad, s.d_smp.p, s.pitch, c->stream, false);
+   s.d_tot = DevMem<uint32_t>(c->N * 4, fn, "the per-sample totals");
+   kern::ld_totals(s.d_smp.p, s.pitch, c->N, s.d_tot.p, c->stream);
 }
 
-void king_launch(int mode, const fpca_ctx *c, const KingScratch &s, uint64_t i0, uint64_t iend, uint64_t j0, uint64_t jend, double *phi, double thr,
+void king_launch(int mode, const fpca_ctx *c, const KingBufs &s, uint64_t i0, uint64_t iend, uint64_t j0, uint64_t jend, double *phi, double thr,
                  uint64_t cap)
 {
    const uint64_t nti = (iend - i0 + KING_TILE - 1) / KING_TILE, ntj = (jend - j0 + KING_TILE - 1) / KING_TILE, wgs = nti * ntj;
    if (!wgs) return;
    if (wgs > 0x7FFFFFFFull || ntj > 0xFFFFFFFFull) throw Error(FPCA_EINVAL, "kinship: " + std::to_string(wgs) + " tile pairs exceed one launch");
    if (mode == KING_BLOCK)
-      hipLaunchKernelGGL(k_king<KING_BLOCK>, dim3((unsigned)wgs), dim3(256), 0, c->stream, s.d_smp, s.pitch, s.d_tot, s.npad, c->N, i0, iend, j0, jend,
-                         (uint32_t)ntj, (int)king_force_general(), phi, s.d_keep, thr, cap, s.d_count, s.d_i, s.d_j, s.d_phi);
+      hipLaunchKernelGGL(k_king<KING_BLOCK>, dim3((unsigned)wgs), dim3(256), 0, c->stream, s.d_smp.p, s.pitch, s.d_tot.p, s.npad, c->N, i0, iend, j0, jend,
+                         (uint32_t)ntj, (int)king_force_general(), phi, s.d_keep.p, thr, cap, s.d_count.p, s.d_i.p, s.d_j.p, s.d_phi.p);
    else
-      hipLaunchKernelGGL(k_king<KING_PAIRS>, dim3((unsigned)wgs), dim3(256), 0, c->stream, s.d_smp, s.pitch, s.d_tot, s.npad, c->N, i0, iend, j0, jend,
-                         (uint32_t)ntj, (int)king_force_general(), phi, s.d_keep, thr, cap, s.d_count, s.d_i, s.d_j, s.d_phi);
+      hipLaunchKernelGGL(k_king<KING_PAIRS>, dim3((unsigned)wgs), dim3(256), 0, c->stream, s.d_smp.p, s.pitch, s.d_tot.p, s.npad, c->N, i0, iend, j0, jend,
+                         (uint32_t)ntj, (int)king_force_general(), phi, s.d_keep.p, thr, cap, s.d_count.p, s.d_i.p, s.d_j.p, s.d_phi.p);
    launch_check();
 }
 
 // the strict upper triangle in slabs of row tiles: slab [ta, tb) x column tiles [ta, nt); the blocks below the diagonal return at once
-void king_triangle(const fpca_ctx *c, const KingScratch &s, double thr, uint64_t cap)
+void king_triangle(const fpca_ctx *c, const KingBufs &s, double thr, uint64_t cap)
 {
    const uint64_t N = c->N, nt = (N + KING_TILE - 1) / KING_TILE;
    uint64_t forced = 0;
@@ -201,29 +192,25 @@ uint64_t king_pair_pass(fpca_ctx *c, const char *fn, const uint8_t *keep, double
    const uint64_t N = c->N;
    cap = std::min<uint64_t>(cap, N * (N - 1) / 2);
    HIP_CHECK(hipSetDevice(c->device));
-   KingScratch s;
+   KingBufs s;
    king_make_operand(c, s, fn);
    if (keep) {
-      HIP_ALLOC(hipMalloc(&s.d_keep, N));
-      HIP_CHECK(hipMemcpyAsync(s.d_keep, keep, N, hipMemcpyHostToDevice, c->stream));
+      s.d_keep = DevMem<uint8_t>(N, fn, "the sample mask");
+      HIP_CHECK(hipMemcpyAsync(s.d_keep.p, keep, N, hipMemcpyHostToDevice, c->stream));
    }
-   const size_t slots = (size_t)std::max<uint64_t>(cap, 1);
-   HIP_ALLOC(hipMalloc(&s.d_i, slots * sizeof(uint32_t)));
-   HIP_ALLOC(hipMalloc(&s.d_j, slots * sizeof(uint32_t)));
-   HIP_ALLOC(hipMalloc(&s.d_phi, slots * sizeof(double)));
-   HIP_ALLOC(hipMalloc(&s.d_count, sizeof(unsigned long long)));
-   HIP_CHECK(hipMemsetAsync(s.d_count, 0, sizeof(unsigned long long), c->stream));
+   s.alloc_pairs((size_t)std::max<uint64_t>(cap, 1), fn);
+   HIP_CHECK(hipMemsetAsync(s.d_count.p, 0, sizeof(unsigned long long), c->stream));
    king_triangle(c, s, thr, cap);
    unsigned long long found = 0;
-   HIP_CHECK(hipMemcpyAsync(&found, s.d_count, sizeof(found), hipMemcpyDeviceToHost, c->stream));
+   HIP_CHECK(hipMemcpyAsync(&found, s.d_count.p, sizeof(found), hipMemcpyDeviceToHost, c->stream));
    HIP_CHECK(hipStreamSynchronize(c->stream));
    out.clear();
    if (found > cap || found == 0) return found;
    std::vector<uint32_t> hi(found), hj(found);
    std::vector<double> hp(found);
-   HIP_CHECK(hipMemcpy(hi.data(), s.d_i, found * sizeof(uint32_t), hipMemcpyDeviceToHost));
-   HIP_CHECK(hipMemcpy(hj.data(), s.d_j, found * sizeof(uint32_t), hipMemcpyDeviceToHost));
-   HIP_CHECK(hipMemcpy(hp.data(), s.d_phi, found * sizeof(double), hipMemcpyDeviceToHost));
+   HIP_CHECK(hipMemcpy(hi.data(), s.d_i.p, found * sizeof(uint32_t), hipMemcpyDeviceToHost));
+   HIP_CHECK(hipMemcpy(hj.data(), s.d_j.p, found * sizeof(uint32_t), hipMemcpyDeviceToHost));
+   HIP_CHECK(hipMemcpy(hp.data(), s.d_phi.p, found * sizeof(double), hipMemcpyDeviceToHost));
    out.resize(found);
    for (uint64_t k = 0; k < found; k++) out[k] = {hi[k], hj[k], hp[k]};
    std::sort(out.begin(), out.end(), [](const KingPair &a, const KingPair &b) { return a.i != b.i ? a.i < b.i : a.j < b.j; });
@@ -303,13 +290,11 @@ extern "C" int fpca_king_block(fpca_ctx *ctx, uint64_t i0, uint64_t ni, uint64_t
                                       std::to_string(KING_BLOCK_LIMIT) + " bytes; call it block by block");
       const size_t count = (size_t)ni * nj;
       HIP_CHECK(hipSetDevice(ctx->device));
-      KingScratch s;
+      KingBufs s;
       king_make_operand(ctx, s, "fpca_king_block");
-      double *d_out = nullptr;
-      HIP_ALLOC(hipMalloc(&d_out, count * sizeof(double)));
-      s.d_phi = d_out; // (released with the scratch)
-      king_launch(KING_BLOCK, ctx, s, i0, i0 + ni, j0, j0 + nj, d_out, 0.0, 0);
-      HIP_CHECK(hipMemcpyAsync(phi, d_out, count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+      DevMem<double> d_out(count, "fpca_king_block", "the block of coefficients");
+      king_launch(KING_BLOCK, ctx, s, i0, i0 + ni, j0, j0 + nj, d_out.p, 0.0, 0);
+      HIP_CHECK(hipMemcpyAsync(phi, d_out.p, count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
       HIP_CHECK(hipStreamSynchronize(ctx->stream));
    });
 }
@@ -379,29 +364,23 @@ extern "C" int fpca_bench_king(fpca_ctx *ctx, int reps, double *ms, double *macs
       HIP_CHECK(hipSetDevice(ctx->device));
       const uint64_t N = ctx->N, cap = 1ull << 20;
       const double thr = 0.0884;
-      KingScratch s;
+      KingBufs s;
       king_make_operand(ctx, s, "fpca_bench_king");
-      HIP_ALLOC(hipMalloc(&s.d_i, cap * sizeof(uint32_t)));
-      HIP_ALLOC(hipMalloc(&s.d_j, cap * sizeof(uint32_t)));
-      HIP_ALLOC(hipMalloc(&s.d_phi, cap * sizeof(double)));
-      HIP_ALLOC(hipMalloc(&s.d_count, sizeof(unsigned long long)));
-      HIP_CHECK(hipEventCreate(&s.e0));
-      HIP_CHECK(hipEventCreate(&s.e1));
-      HIP_CHECK(hipMemsetAsync(s.d_count, 0, sizeof(unsigned long long), ctx->stream));
+      s.alloc_pairs(cap, "fpca_bench_king");
+      DevEvent e0("fpca_bench_king"), e1("fpca_bench_king");
+      HIP_CHECK(hipMemsetAsync(s.d_count.p, 0, sizeof(unsigned long long), ctx->stream));
       king_triangle(ctx, s, thr, cap);
       for (int r = 0; r < reps; r++) {
-         HIP_CHECK(hipMemsetAsync(s.d_count, 0, sizeof(unsigned long long), ctx->stream));
-         HIP_CHECK(hipEventRecord(s.e0, ctx->stream));
+         HIP_CHECK(hipMemsetAsync(s.d_count.p, 0, sizeof(unsigned long long), ctx->stream));
+         HIP_CHECK(hipEventRecord(e0, ctx->stream));
          king_triangle(ctx, s, thr, cap);
-         HIP_CHECK(hipEventRecord(s.e1, ctx->stream));
-         HIP_CHECK(hipEventSynchronize(s.e1));
-         float t = 0;
-         HIP_CHECK(hipEventElapsedTime(&t, s.e0, s.e1));
-         ms[r] = t;
+         HIP_CHECK(hipEventRecord(e1, ctx->stream));
+         HIP_CHECK(hipEventSynchronize(e1));
+         ms[r] = elapsed_ms(e0, e1);
       }
       if (macs) { // the kernel's own wave-level decisions, replayed on the host
          std::vector<uint32_t> h_tot(N * 4);
-         HIP_CHECK(hipMemcpy(h_tot.data(), s.d_tot, N * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+         HIP_CHECK(hipMemcpy(h_tot.data(), s.d_tot.p, N * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
          const uint64_t nb = (N + 31) / 32; // the waves' 32-sample blocks start at multiples of 32
          std::vector<uint8_t> clean(nb, 1);
          for (uint64_t b = 0; b < nb; b++)

@@ -150,42 +150,22 @@ bool ld_force_general()
 }
 
 // device buffers of one call
-struct LdScratch {
-   uint32_t *d_tot = nullptr, *d_bits = nullptr;
-   double *d_r2 = nullptr;
-   hipEvent_t e0 = nullptr, e1 = nullptr;
-   ~LdScratch()
-   {
-      if (d_tot) (void)hipFree(d_tot);
-      if (d_bits) (void)hipFree(d_bits);
-      if (d_r2) (void)hipFree(d_r2);
-      if (e0) (void)hipEventDestroy(e0);
-      if (e1) (void)hipEventDestroy(e1);
-   }
+struct LdBufs {
+   DevMem<uint32_t> d_tot, d_bits;
 };
 
 // totals of records [r0, r0 + nrec), at their own record numbers (the kernel indexes them absolutely)
-void ld_make_totals(fpca_ctx *c, LdScratch &s, uint64_t r0, uint64_t nrec)
+void ld_make_totals(fpca_ctx *c, LdBufs &s, const char *fn, uint64_t r0, uint64_t nrec)
 {
-   HIP_ALLOC(hipMalloc(&s.d_tot, c->P_g * 4 * sizeof(uint32_t)));
-   kern::ld_totals(c->d_packed + r0 * c->pitch, c->pitch, nrec, s.d_tot + r0 * 4, c->stream);
+   s.d_tot = DevMem<uint32_t>(c->P_g * 4, fn, "the per-SNP totals");
+   kern::ld_totals(c->d_packed + r0 * c->pitch, c->pitch, nrec, s.d_tot.p + r0 * 4, c->stream);
 }
 
-void ld_alloc_bits(fpca_ctx *c, LdScratch &s, const char *fn, uint64_t rows, uint32_t words)
+void ld_alloc_bits(fpca_ctx *c, LdBufs &s, const char *fn, uint64_t rows, uint32_t words)
 {
-   const size_t need = (size_t)rows * words * sizeof(uint32_t);
-   const hipError_t e = hipMalloc(&s.d_bits, need);
-   if (e == hipErrorOutOfMemory) {
-      (void)hipGetLastError();
-      size_t fr = 0, tot = 0;
-      (void)hipMemGetInfo(&fr, &tot);
-      const double mb = 1.0 / (1024.0 * 1024.0);
-      char msg[384];
-      std::snprintf(msg, sizeof(msg), "%s: the band bitmap needs %.1f MiB of device memory (%llu SNPs x %u words); %.1f of %.1f MiB are free on device %d", fn,
-                    (double)need * mb, (unsigned long long)rows, words, (double)fr * mb, (double)tot * mb, c->device);
-      throw Error(FPCA_ENOMEM, msg);
-   }
-   if (e != hipSuccess) throw Error(FPCA_EHIP, std::string("hipMalloc of the band bitmap failed: ") + hipGetErrorString(e));
+   char detail[96];
+   std::snprintf(detail, sizeof(detail), "%llu SNPs x %u words", (unsigned long long)rows, words);
+   s.d_bits = DevMem<uint32_t>((size_t)rows * words, fn, "band bitmap", 0, detail, c->device);
 }
 
 } // namespace
@@ -287,13 +267,13 @@ extern "C" int fpca_ld_band(fpca_ctx *ctx, uint64_t snp0, uint64_t nsnp, uint32_
                                       " SNPs at this span); call it range by range");
       const size_t count = (size_t)nsnp * span;
       HIP_CHECK(hipSetDevice(ctx->device));
-      LdScratch s;
-      ld_make_totals(ctx, s, snp0, nsnp);
-      HIP_ALLOC(hipMalloc(&s.d_r2, count * sizeof(double)));
-      HIP_CHECK(hipMemsetAsync(s.d_r2, 0xFF, count * sizeof(double), ctx->stream)); // (a NaN pattern; the host rewrites what no pair owns)
-      kern::ld_band(ctx->d_packed, ctx->pitch, s.d_tot, (uint32_t)(ctx->N_pad - ctx->N), snp0, nsnp, snp0 + nsnp, span, s.d_r2, nullptr, 0, 0.0,
+      LdBufs s;
+      ld_make_totals(ctx, s, "fpca_ld_band", snp0, nsnp);
+      DevMem<double> d_r2(count, "fpca_ld_band", "the band of r2");
+      HIP_CHECK(hipMemsetAsync(d_r2.p, 0xFF, count * sizeof(double), ctx->stream)); // (a NaN pattern; the host rewrites what no pair owns)
+      kern::ld_band(ctx->d_packed, ctx->pitch, s.d_tot.p, (uint32_t)(ctx->N_pad - ctx->N), snp0, nsnp, snp0 + nsnp, span, d_r2.p, nullptr, 0, 0.0,
                     ld_force_general(), ctx->stream);
-      HIP_CHECK(hipMemcpyAsync(r2, s.d_r2, count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+      HIP_CHECK(hipMemcpyAsync(r2, d_r2.p, count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
       HIP_CHECK(hipStreamSynchronize(ctx->stream));
       const double nan = std::nan("");
       for (uint64_t i = nsnp > span ? nsnp - span : 0; i < nsnp; i++) // positions past the last SNP of the range
@@ -319,19 +299,19 @@ extern "C" int fpca_ld_prune(fpca_ctx *ctx, const uint32_t *chrom, uint32_t wind
          if (std::atoll(v) > 0) slab = (uint64_t)std::atoll(v);
       slab = std::min(slab, P);
       const auto t0 = std::chrono::steady_clock::now();
-      LdScratch s;
-      ld_make_totals(ctx, s, 0, ctx->P_g);
+      LdBufs s;
+      ld_make_totals(ctx, s, "fpca_ld_prune", 0, ctx->P_g);
       ld_alloc_bits(ctx, s, "fpca_ld_prune", slab, words);
       std::vector<uint32_t> h_tot(P * 4), h_bits(P * words);
       std::vector<double> maf(P);
-      HIP_CHECK(hipMemcpyAsync(h_tot.data(), s.d_tot, P * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+      HIP_CHECK(hipMemcpyAsync(h_tot.data(), s.d_tot.p, P * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
       HIP_CHECK(hipMemcpyAsync(maf.data(), ctx->d_mean, P * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
       for (uint64_t b = 0; b < P; b += slab) {
          const uint64_t nb = std::min(slab, P - b);
-         HIP_CHECK(hipMemsetAsync(s.d_bits, 0, nb * words * sizeof(uint32_t), ctx->stream));
-         kern::ld_band(ctx->d_packed, ctx->pitch, s.d_tot, (uint32_t)(ctx->N_pad - ctx->N), b, nb, P, span, nullptr, s.d_bits, words, r2, ld_force_general(),
+         HIP_CHECK(hipMemsetAsync(s.d_bits.p, 0, nb * words * sizeof(uint32_t), ctx->stream));
+         kern::ld_band(ctx->d_packed, ctx->pitch, s.d_tot.p, (uint32_t)(ctx->N_pad - ctx->N), b, nb, P, span, nullptr, s.d_bits.p, words, r2, ld_force_general(),
                        ctx->stream);
-         HIP_CHECK(hipMemcpyAsync(h_bits.data() + b * words, s.d_bits, nb * words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+         HIP_CHECK(hipMemcpyAsync(h_bits.data() + b * words, s.d_bits.p, nb * words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
       }
       HIP_CHECK(hipStreamSynchronize(ctx->stream));
       const auto t1 = std::chrono::steady_clock::now();
@@ -374,25 +354,22 @@ extern "C" int fpca_bench_ld(fpca_ctx *ctx, uint32_t span, int reps, double *ms,
       HIP_CHECK(hipSetDevice(ctx->device));
       const uint64_t P = ctx->P_g;
       const uint32_t words = (span + 31) / 32, npad = (uint32_t)(ctx->N_pad - ctx->N);
-      LdScratch s;
-      ld_make_totals(ctx, s, 0, ctx->P_g);
+      LdBufs s;
+      ld_make_totals(ctx, s, "fpca_bench_ld", 0, ctx->P_g);
       ld_alloc_bits(ctx, s, "fpca_bench_ld", P, words);
-      HIP_CHECK(hipEventCreate(&s.e0));
-      HIP_CHECK(hipEventCreate(&s.e1));
-      HIP_CHECK(hipMemsetAsync(s.d_bits, 0, (size_t)P * words * sizeof(uint32_t), ctx->stream));
-      kern::ld_band(ctx->d_packed, ctx->pitch, s.d_tot, npad, 0, P, P, span, nullptr, s.d_bits, words, 0.05, ld_force_general(), ctx->stream);
+      DevEvent e0("fpca_bench_ld"), e1("fpca_bench_ld");
+      HIP_CHECK(hipMemsetAsync(s.d_bits.p, 0, (size_t)P * words * sizeof(uint32_t), ctx->stream));
+      kern::ld_band(ctx->d_packed, ctx->pitch, s.d_tot.p, npad, 0, P, P, span, nullptr, s.d_bits.p, words, 0.05, ld_force_general(), ctx->stream);
       for (int r = 0; r < reps; r++) {
-         HIP_CHECK(hipEventRecord(s.e0, ctx->stream));
-         kern::ld_band(ctx->d_packed, ctx->pitch, s.d_tot, npad, 0, P, P, span, nullptr, s.d_bits, words, 0.05, ld_force_general(), ctx->stream);
-         HIP_CHECK(hipEventRecord(s.e1, ctx->stream));
-         HIP_CHECK(hipEventSynchronize(s.e1));
-         float t = 0;
-         HIP_CHECK(hipEventElapsedTime(&t, s.e0, s.e1));
-         ms[r] = t;
+         HIP_CHECK(hipEventRecord(e0, ctx->stream));
+         kern::ld_band(ctx->d_packed, ctx->pitch, s.d_tot.p, npad, 0, P, P, span, nullptr, s.d_bits.p, words, 0.05, ld_force_general(), ctx->stream);
+         HIP_CHECK(hipEventRecord(e1, ctx->stream));
+         HIP_CHECK(hipEventSynchronize(e1));
+         ms[r] = elapsed_ms(e0, e1);
       }
       if (macs) { // the kernel's own wave-level decisions, replayed on the host
          std::vector<uint32_t> h_tot(P * 4);
-         HIP_CHECK(hipMemcpy(h_tot.data(), s.d_tot, P * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+         HIP_CHECK(hipMemcpy(h_tot.data(), s.d_tot.p, P * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
          auto clean = [&](uint64_t a) {
             for (uint64_t l = 0; l < 32; l++)
                if (h_tot[4 * std::min(a + l, P - 1) + 2] != npad) return false;

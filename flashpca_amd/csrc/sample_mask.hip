@@ -149,17 +149,15 @@ namespace fpca {
 
 void masked_stats(fpca_ctx *c)
 {
-   uint32_t *d_nmiss = nullptr;
    std::vector<uint32_t> nm(c->P_g);
    std::vector<double> ss(c->P_g);
    if (c->P_g) {
-      HIP_CHECK(hipMalloc(&d_nmiss, c->P_g * sizeof(uint32_t)));
+      DevMem<uint32_t> d_nmiss(c->P_g, "fpca_set_sample_mask", "the per-SNP missing counts");
       hipLaunchKernelGGL(k_bed_stats_masked, dim3((unsigned)c->P_g), dim3(256), 0, c->stream, c->d_packed, c->pitch, c->d_keep_bits, c->N, c->stand,
-                         c->d_lut, c->d_mean, c->d_sd, c->d_sumsq, d_nmiss);
+                         c->d_lut, c->d_mean, c->d_sd, c->d_sumsq, d_nmiss.p);
       const hipError_t e[3] = {hipGetLastError(), hipMemcpyAsync(ss.data(), c->d_sumsq, c->P_g * sizeof(double), hipMemcpyDeviceToHost, c->stream),
-                               hipMemcpyAsync(nm.data(), d_nmiss, c->P_g * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream)};
-      const hipError_t es = hipStreamSynchronize(c->stream);
-      (void)hipFree(d_nmiss);
+                               hipMemcpyAsync(nm.data(), d_nmiss.p, c->P_g * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream)};
+      const hipError_t es = hipStreamSynchronize(c->stream); // (before anything is reported: d_nmiss is freed on the way out)
       for (hipError_t x : e) HIP_CHECK(x);
       HIP_CHECK(es);
    }
@@ -167,14 +165,7 @@ void masked_stats(fpca_ctx *c)
    for (uint32_t v : nm) c->n_missing += v;
    c->missing_known = true;
    c->h_nmiss.swap(nm);
-   double tot = 0; // (blocked summation, as ensure_stats)
-   for (size_t i0 = 0; i0 < ss.size(); i0 += 1024) {
-      double sblk = 0;
-      const size_t i1 = std::min(ss.size(), i0 + 1024);
-      for (size_t i = i0; i < i1; i++) sblk += ss[i];
-      tot += sblk;
-   }
-   c->trace_local = tot;
+   c->trace_local = blocked_sum(ss.data(), ss.size()); // (as ensure_stats)
    c->i8_scales_done = false;
    c->stats_done = true;
 }
@@ -251,25 +242,16 @@ extern "C" int fpca_set_sample_mask(fpca_ctx *ctx, const uint8_t *keep)
                                      " samples; at least 2 are needed");
       HIP_CHECK(hipSetDevice(ctx->device));
       HIP_CHECK(hipStreamSynchronize(ctx->stream));
-      uint8_t *d_rows = nullptr, *d_bits = nullptr;
-      uint32_t *d_idx = nullptr;
-      try {
-         HIP_ALLOC(hipMalloc(&d_rows, rows.size()));
-         HIP_ALLOC(hipMalloc(&d_bits, bits.size()));
-         HIP_ALLOC(hipMalloc(&d_idx, idx.size() * sizeof(uint32_t)));
-         HIP_CHECK(hipMemcpy(d_rows, rows.data(), rows.size(), hipMemcpyHostToDevice));
-         HIP_CHECK(hipMemcpy(d_bits, bits.data(), bits.size(), hipMemcpyHostToDevice));
-         HIP_CHECK(hipMemcpy(d_idx, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-      } catch (...) {
-         if (d_rows) (void)hipFree(d_rows);
-         if (d_bits) (void)hipFree(d_bits);
-         if (d_idx) (void)hipFree(d_idx);
-         throw;
-      }
-      free_mask(ctx);
-      ctx->d_keep = d_rows;
-      ctx->d_keep_bits = d_bits;
-      ctx->d_keep_idx = d_idx;
+      static const char *FN = "fpca_set_sample_mask";
+      DevMem<uint8_t> d_rows(rows.size(), FN, "the row mask"), d_bits(bits.size(), FN, "the mask row of the statistics pass");
+      DevMem<uint32_t> d_idx(idx.size(), FN, "the kept-sample list");
+      HIP_CHECK(hipMemcpy(d_rows.p, rows.data(), rows.size(), hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(d_bits.p, bits.data(), bits.size(), hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(d_idx.p, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+      free_mask(ctx); // all three uploads are in: the context takes them
+      ctx->d_keep = d_rows.release();
+      ctx->d_keep_bits = d_bits.release();
+      ctx->d_keep_idx = d_idx.release();
       ctx->n_kept = idx.size();
       ctx->h_keep_idx.swap(idx);
       ctx->stats_done = false;

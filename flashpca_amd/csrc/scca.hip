@@ -377,26 +377,16 @@ static void scca_prepare(fpca_ctx *c, const double *Y, int64_t ldy, int k, int s
    st->k = k;
    st->kp = kp;
    st->invdiv = divisor == FPCA_DIVISOR_N1 ? 1.0 / std::sqrt((double)N - 1.0) : 1.0;
-   const size_t cbytes = (size_t)P * kp * sizeof(double);
-   {
-      const hipError_t e = hipMalloc(&st->d_C, std::max<size_t>(cbytes, 8));
-      if (e != hipSuccess) {
-         (void)hipGetLastError();
-         st->d_C = nullptr;
-         throw Error(e == hipErrorOutOfMemory ? FPCA_ENOMEM : FPCA_EHIP,
-                     "fpca_scca_prepare: the " + std::to_string(P) + " x " + std::to_string(k) + " cross-product matrix (" + std::to_string(cbytes) +
-                        " bytes) does not fit in device memory");
-      }
-   }
-   HIP_ALLOC(hipMalloc(&st->d_flags, 16));
+   // (the state owns both, scca.hpp)
+   st->d_C = static_cast<double *>(dev_alloc(std::max<size_t>((size_t)P * kp * sizeof(double), 8), "fpca_scca_prepare",
+                                             ("the " + std::to_string(P) + " x " + std::to_string(k) + " cross-product matrix").c_str()));
+   st->d_flags = static_cast<int *>(dev_alloc(16, "fpca_scca_prepare", "the iteration flags"));
 
    // phenotypes: rows of a [k][N_pad] image, standardised there (util.cpp:24-110), back as N x k, scaled
    st->Yh.resize((size_t)N * k);
    {
-      double *dY = nullptr;
-      HIP_ALLOC(hipMalloc(&dY, ((size_t)k * c->N_pad + 3 * (size_t)k) * sizeof(double)));
-      std::unique_ptr<double, void (*)(double *)> guard(dY, [](double *p) { (void)hipFree(p); });
-      double *dstat = dY + (size_t)k * c->N_pad;
+      DevMem<double> own((size_t)k * c->N_pad + 3 * (size_t)k, "fpca_scca_prepare", "the phenotypes");
+      double *dY = own.p, *dstat = dY + (size_t)k * c->N_pad;
       HIP_CHECK(hipMemcpy2DAsync(dY, c->N_pad * sizeof(double), Y, (size_t)ldy * sizeof(double), N * sizeof(double), k, hipMemcpyHostToDevice, s));
       kern::dense_standardise(dY, c->N_pad, N, k, stand_y, dstat, dstat + k, dstat + 2 * k, s);
       HIP_CHECK(hipMemcpy2DAsync(st->Yh.data(), N * sizeof(double), dY, c->N_pad * sizeof(double), N * sizeof(double), k, hipMemcpyDeviceToHost, s));
@@ -450,7 +440,7 @@ void scca_fit_dev(fpca_ctx *c, fpca_scca_state *st, double lambda1, double lambd
       if (st->d_ws) (void)hipFree(st->d_ws);
       st->d_ws = nullptr;
       st->ws_cap = 0;
-      HIP_ALLOC(hipMalloc(&st->d_ws, total * sizeof(double)));
+      st->d_ws = static_cast<double *>(dev_alloc(total * sizeof(double), "fpca_scca_fit / fpca_scca_cv", "the workspace of a fit")); // (the state's)
       st->ws_cap = total;
    }
    double *dU = st->d_ws + oU, *dt = st->d_ws + ot, *dV = st->d_ws + oV, *dG = st->d_ws + oG, *pA = st->d_ws + oA, *pN = st->d_ws + oN,

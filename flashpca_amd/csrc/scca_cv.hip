@@ -248,58 +248,35 @@ int chunk_width(int nc) { return nc <= 16 ? 16 : nc <= 32 ? 32 : 64; }
 
 unsigned grid_for(uint64_t total) { return (unsigned)std::min<uint64_t>(8192, std::max<uint64_t>(1, (total + 255) / 256)); }
 
-// device buffers of one call, released on every way out
-struct DevBufs {
-   std::vector<void *> ptrs;
-   template <typename T> T *get(size_t count, const char *fn, const char *what)
-   {
-      void *p = nullptr;
-      const size_t bytes = std::max<size_t>(count * sizeof(T), 8);
-      const hipError_t e = hipMalloc(&p, bytes);
-      if (e != hipSuccess) {
-         (void)hipGetLastError();
-         throw Error(e == hipErrorOutOfMemory ? FPCA_ENOMEM : FPCA_EHIP,
-                     std::string(fn) + ": " + what + " (" + std::to_string(bytes) + " bytes) does not fit in device memory");
-      }
-      ptrs.push_back(p);
-      return static_cast<T *>(p);
-   }
-   ~DevBufs()
-   {
-      for (void *p : ptrs) (void)hipFree(p);
-   }
-};
-
 // the context's standardisation while the folds swap it: saved before the first fold, put back on EVERY way out
 struct StatsGuard {
    fpca_ctx *c;
-   double *save = nullptr; // mean | sd | sumsq [P_pad each] | lut [4 P_pad]
+   DevMem<double> own; // mean | sd | sumsq [P_pad each] | lut [4 P_pad]
    double trace_local;
    bool stats_done, missing_known;
-   explicit StatsGuard(fpca_ctx *ctx) : c(ctx), trace_local(ctx->trace_local), stats_done(ctx->stats_done), missing_known(ctx->missing_known)
+   explicit StatsGuard(fpca_ctx *ctx)
+      : c(ctx), own(7 * ctx->P_pad, "fpca_scca_cv", "the copy of the context's mean / sd"), trace_local(ctx->trace_local), stats_done(ctx->stats_done),
+        missing_known(ctx->missing_known)
    {
       const size_t n = c->P_pad;
-      HIP_ALLOC(hipMalloc(&save, 7 * n * sizeof(double)));
+      double *save = own.p;
       const hipError_t e[4] = {hipMemcpyAsync(save, c->d_mean, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream),
                                hipMemcpyAsync(save + n, c->d_sd, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream),
                                hipMemcpyAsync(save + 2 * n, c->d_sumsq, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream),
                                hipMemcpyAsync(save + 3 * n, c->d_lut, 4 * n * sizeof(double), hipMemcpyDeviceToDevice, c->stream)};
       for (hipError_t x : e)
-         if (x != hipSuccess) {
-            (void)hipFree(save);
-            throw Error(FPCA_EHIP, std::string("saving the context's mean / sd failed: ") + hipGetErrorString(x));
-         }
+         if (x != hipSuccess) throw Error(FPCA_EHIP, std::string("saving the context's mean / sd failed: ") + hipGetErrorString(x));
    }
-   ~StatsGuard()
+   ~StatsGuard() // synchronise, copy back, synchronise; `own` is freed after this body
    {
       const size_t n = c->P_pad;
+      const double *save = own.p;
       (void)hipStreamSynchronize(c->stream);
       (void)hipMemcpyAsync(c->d_mean, save, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
       (void)hipMemcpyAsync(c->d_sd, save + n, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
       (void)hipMemcpyAsync(c->d_sumsq, save + 2 * n, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
       (void)hipMemcpyAsync(c->d_lut, save + 3 * n, 4 * n * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
       (void)hipStreamSynchronize(c->stream);
-      (void)hipFree(save);
       c->i8_scales_done = false;
       c->trace_local = trace_local;
       c->stats_done = stats_done;
@@ -401,43 +378,32 @@ void scca_cv(fpca_ctx *c, const CvArgs &a)
    ensure_io(c);
    c->ensure(c->d_T, c->T_cap, (size_t)c->P_pad * MAX_BLOCKVEC);
 
-   DevBufs bufs;
    fpca_scca_state st;
    st.k = k;
    st.kp = kp;
-   {
-      const size_t cbytes = std::max<size_t>((size_t)P * kp * sizeof(double), 8);
-      const hipError_t e = hipMalloc(&st.d_C, cbytes);
-      if (e != hipSuccess) {
-         (void)hipGetLastError();
-         st.d_C = nullptr;
-         throw Error(e == hipErrorOutOfMemory ? FPCA_ENOMEM : FPCA_EHIP, std::string(FN) + ": the " + std::to_string(P) + " x " + std::to_string(k) +
-                                                                            " cross-product matrix (" + std::to_string(cbytes) +
-                                                                            " bytes) does not fit in device memory");
-      }
-   }
-   HIP_ALLOC(hipMalloc(&st.d_flags, 16));
-   uint8_t *d_masks = bufs.get<uint8_t>(masks.size(), FN, "the fold masks");
-   uint8_t *d_fold = bufs.get<uint8_t>(N, FN, "the fold ids");
-   uint32_t *d_counts = bufs.get<uint32_t>((size_t)nfolds * P * 3, FN, "the per-fold genotype counts");
-   double *d_Yraw = bufs.get<double>((size_t)k * c->N_pad, FN, "the phenotypes");
-   double *d_Ys = bufs.get<double>((size_t)k * c->N_pad, FN, "the standardised phenotypes");
-   double *d_Uall = bufs.get<double>((size_t)ncols * P, FN, "the workspace for a fold's U");
-   double *d_Vall = bufs.get<double>((size_t)ncols * kp, FN, "the workspace for a fold's V");
-   int *d_conv = bufs.get<int>((size_t)ncell, FN, "the convergence flags");
-   uint32_t *d_nz = bufs.get<uint32_t>((size_t)ncols, FN, "the non-zero counts");
-   double *d_xpred = bufs.get<double>((size_t)ncols * N, FN, "xpred, the held-out projections of the genotypes");
-   double *d_ypred = bufs.get<double>((size_t)ncols * N, FN, "ypred, the held-out projections of the phenotypes");
-   double *d_corr = bufs.get<double>((size_t)ncols, FN, "the correlations");
+   // (the state owns both, scca.hpp)
+   st.d_C = static_cast<double *>(dev_alloc(std::max<size_t>((size_t)P * kp * sizeof(double), 8), FN,
+                                            ("the " + std::to_string(P) + " x " + std::to_string(k) + " cross-product matrix").c_str()));
+   st.d_flags = static_cast<int *>(dev_alloc(16, FN, "the iteration flags"));
+   // (a buffer of no element is 8 bytes: every kernel is handed a pointer)
+   DevMem<uint8_t> d_masks(masks.size(), FN, "the fold masks", 8), d_fold(N, FN, "the fold ids", 8);
+   DevMem<uint32_t> d_counts((size_t)nfolds * P * 3, FN, "the per-fold genotype counts", 8);
+   DevMem<double> d_Yraw((size_t)k * c->N_pad, FN, "the phenotypes", 8), d_Ys((size_t)k * c->N_pad, FN, "the standardised phenotypes", 8);
+   DevMem<double> d_Uall((size_t)ncols * P, FN, "the workspace for a fold's U", 8), d_Vall((size_t)ncols * kp, FN, "the workspace for a fold's V", 8);
+   DevMem<int> d_conv((size_t)ncell, FN, "the convergence flags", 8);
+   DevMem<uint32_t> d_nz((size_t)ncols, FN, "the non-zero counts", 8);
+   DevMem<double> d_xpred((size_t)ncols * N, FN, "xpred, the held-out projections of the genotypes", 8);
+   DevMem<double> d_ypred((size_t)ncols * N, FN, "ypred, the held-out projections of the phenotypes", 8);
+   DevMem<double> d_corr((size_t)ncols, FN, "the correlations", 8);
 
-   HIP_CHECK(hipMemcpyAsync(d_masks, masks.data(), masks.size(), hipMemcpyHostToDevice, s));
-   HIP_CHECK(hipMemcpyAsync(d_fold, a.fold, N, hipMemcpyHostToDevice, s));
-   HIP_CHECK(hipMemcpy2DAsync(d_Yraw, c->N_pad * sizeof(double), a.Y, (size_t)a.ldy * sizeof(double), N * sizeof(double), k, hipMemcpyHostToDevice, s));
-   HIP_CHECK(hipMemsetAsync(d_xpred, 0, (size_t)ncols * N * sizeof(double), s)); // scca.R:447-448
-   HIP_CHECK(hipMemsetAsync(d_ypred, 0, (size_t)ncols * N * sizeof(double), s));
+   HIP_CHECK(hipMemcpyAsync(d_masks.p, masks.data(), masks.size(), hipMemcpyHostToDevice, s));
+   HIP_CHECK(hipMemcpyAsync(d_fold.p, a.fold, N, hipMemcpyHostToDevice, s));
+   HIP_CHECK(hipMemcpy2DAsync(d_Yraw.p, c->N_pad * sizeof(double), a.Y, (size_t)a.ldy * sizeof(double), N * sizeof(double), k, hipMemcpyHostToDevice, s));
+   HIP_CHECK(hipMemsetAsync(d_xpred.p, 0, (size_t)ncols * N * sizeof(double), s)); // scca.R:447-448
+   HIP_CHECK(hipMemsetAsync(d_ypred.p, 0, (size_t)ncols * N * sizeof(double), s));
    HIP_CHECK(hipStreamSynchronize(s));
    lap(-1);
-   launch_fold_counts(c, d_masks, nfolds, d_counts, s);
+   launch_fold_counts(c, d_masks.p, nfolds, d_counts.p, s);
    lap(0);
 
    StatsGuard guard(c);
@@ -446,18 +412,18 @@ void scca_cv(fpca_ctx *c, const CvArgs &a)
    std::vector<uint32_t> hnz(ncols);
    for (int f = 0; f < nfolds; f++) {
       // the training standardisation of the genotypes, installed as fpca_set_meansd installs one
-      launch_fold_meansd(c, d_counts, nfolds, f, c->d_mean, c->d_sd, s);
+      launch_fold_meansd(c, d_counts.p, nfolds, f, c->d_mean, c->d_sd, s);
       kern::lut_from_meansd(c->d_mean, c->d_sd, P, c->d_lut, s);
       c->i8_scales_done = false;
       // ... and of the phenotypes
-      hipLaunchKernelGGL(k_cv_stand_y, dim3((unsigned)k), dim3(256), 0, s, d_Yraw, d_Ys, c->N_pad, N, d_fold, f, a.stand_y);
+      hipLaunchKernelGGL(k_cv_stand_y, dim3((unsigned)k), dim3(256), 0, s, d_Yraw.p, d_Ys.p, c->N_pad, N, d_fold.p, f, a.stand_y);
       HIP_CHECK(hipGetLastError());
       st.invdiv = a.divisor == FPCA_DIVISOR_N1 ? 1.0 / std::sqrt((double)(N - fsize[f]) - 1.0) : 1.0;
       lap(1);
       // C_f = invdiv^2 X[T]' Y[T]: the chunked K2 pass of fpca_scca_prepare on an operand whose held-out rows are zero
       for (int c0 = 0; c0 < k; c0 += MAX_BLOCKVEC) {
          const int nc = std::min(MAX_BLOCKVEC, k - c0), bw = chunk_width(nc);
-         hipLaunchKernelGGL(k_cv_operand, dim3(grid_for(c->N_pad * bw)), dim3(256), 0, s, d_Ys, c->N_pad, N, c0, nc, bw, st.invdiv, d_fold, f, c->d_io_a);
+         hipLaunchKernelGGL(k_cv_operand, dim3(grid_for(c->N_pad * bw)), dim3(256), 0, s, d_Ys.p, c->N_pad, N, c0, nc, bw, st.invdiv, d_fold.p, f, c->d_io_a);
          HIP_CHECK(hipGetLastError());
          xt_dev(c, c->d_io_a, bw, s);
          scca_store_c(c->d_T, P, bw, nc, st.invdiv, st.d_C, kp, c0, s);
@@ -482,19 +448,19 @@ void scca_cv(fpca_ctx *c, const CvArgs &a)
       }
       for (int cell = 0; cell < ncell; cell++) {
          scca_fit_dev(c, &st, a.l1[cell / a.n2], a.l2[cell % a.n2], ndim, a.maxiter, a.tol, Vs, ldvs, fit);
-         HIP_CHECK(hipMemcpyAsync(d_Uall + (size_t)cell * ndim * P, fit.dU, (size_t)ndim * P * sizeof(double), hipMemcpyDeviceToDevice, s));
-         HIP_CHECK(hipMemcpyAsync(d_Vall + (size_t)cell * ndim * kp, fit.dV, (size_t)ndim * kp * sizeof(double), hipMemcpyDeviceToDevice, s));
+         HIP_CHECK(hipMemcpyAsync(d_Uall.p + (size_t)cell * ndim * P, fit.dU, (size_t)ndim * P * sizeof(double), hipMemcpyDeviceToDevice, s));
+         HIP_CHECK(hipMemcpyAsync(d_Vall.p + (size_t)cell * ndim * kp, fit.dV, (size_t)ndim * kp * sizeof(double), hipMemcpyDeviceToDevice, s));
          fconv[cell] = conv[(size_t)f * ncell + cell] = fit.converged;
          for (int q = 0; q < ndim; q++) {
             iters[((size_t)f * ncell + cell) * ndim + q] = fit.iters[q];
             total_iters += fit.iters[q];
          }
       }
-      HIP_CHECK(hipMemcpyAsync(d_conv, fconv.data(), (size_t)ncell * sizeof(int), hipMemcpyHostToDevice, s));
-      hipLaunchKernelGGL(k_cv_count_nz, dim3((unsigned)ncols), dim3(256), 0, s, d_Uall, P, d_nz);
+      HIP_CHECK(hipMemcpyAsync(d_conv.p, fconv.data(), (size_t)ncell * sizeof(int), hipMemcpyHostToDevice, s));
+      hipLaunchKernelGGL(k_cv_count_nz, dim3((unsigned)ncols), dim3(256), 0, s, d_Uall.p, P, d_nz.p);
       HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipMemcpyAsync(hnz.data(), d_nz, (size_t)ncols * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipMemcpyAsync(hV.data(), d_Vall, (size_t)ncols * kp * sizeof(double), hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(hnz.data(), d_nz.p, (size_t)ncols * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(hV.data(), d_Vall.p, (size_t)ncols * kp * sizeof(double), hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipStreamSynchronize(s));
       for (int col = 0; col < ncols; col++) { // scca.R:516-523: the mean over the folds
          nzx[col] += (double)hnz[col];
@@ -507,21 +473,21 @@ void scca_cv(fpca_ctx *c, const CvArgs &a)
       if (fsize[f]) {
          for (int c0 = 0; c0 < ncols; c0 += MAX_BLOCKVEC) {
             const int nc = std::min(MAX_BLOCKVEC, ncols - c0), bw = chunk_width(nc);
-            kern::colmajor_to_t(d_Uall + (size_t)c0 * P, P, P, c->P_pad, bw, nc, c->d_T, s);
+            kern::colmajor_to_t(d_Uall.p + (size_t)c0 * P, P, P, c->P_pad, bw, nc, c->d_T, s);
             x_dev(c, bw, c->d_io_b, s);
-            hipLaunchKernelGGL(k_cv_gather_x, dim3(grid_for(N * nc)), dim3(256), 0, s, c->d_io_b, bw, nc, N, d_fold, f, d_conv, ndim, c0, d_xpred);
+            hipLaunchKernelGGL(k_cv_gather_x, dim3(grid_for(N * nc)), dim3(256), 0, s, c->d_io_b, bw, nc, N, d_fold.p, f, d_conv.p, ndim, c0, d_xpred.p);
             HIP_CHECK(hipGetLastError());
          }
-         hipLaunchKernelGGL(k_cv_ypred, dim3(grid_for(N * ncols)), dim3(256), 0, s, d_Ys, c->N_pad, N, k, d_Vall, kp, ncols, d_fold, f, d_conv, ndim, d_ypred);
+         hipLaunchKernelGGL(k_cv_ypred, dim3(grid_for(N * ncols)), dim3(256), 0, s, d_Ys.p, c->N_pad, N, k, d_Vall.p, kp, ncols, d_fold.p, f, d_conv.p, ndim, d_ypred.p);
          HIP_CHECK(hipGetLastError());
       }
       HIP_CHECK(hipStreamSynchronize(s)); // (fconv is reused by the next fold)
       lap(4);
    }
-   hipLaunchKernelGGL(k_cv_corr, dim3((unsigned)ncols), dim3(256), 0, s, d_xpred, d_ypred, N, d_corr);
+   hipLaunchKernelGGL(k_cv_corr, dim3((unsigned)ncols), dim3(256), 0, s, d_xpred.p, d_ypred.p, N, d_corr.p);
    HIP_CHECK(hipGetLastError());
    std::vector<double> hcorr(ncols);
-   HIP_CHECK(hipMemcpyAsync(hcorr.data(), d_corr, (size_t)ncols * sizeof(double), hipMemcpyDeviceToHost, s));
+   HIP_CHECK(hipMemcpyAsync(hcorr.data(), d_corr.p, (size_t)ncols * sizeof(double), hipMemcpyDeviceToHost, s));
    HIP_CHECK(hipStreamSynchronize(s));
    lap(5);
 
@@ -551,8 +517,8 @@ void scca_cv(fpca_ctx *c, const CvArgs &a)
    if (a.best_corr) *a.best_corr = best;
    if (a.best_l1) *a.best_l1 = b1;
    if (a.best_l2) *a.best_l2 = b2;
-   if (a.xpred) HIP_CHECK(hipMemcpy(a.xpred, d_xpred, (size_t)ncols * N * sizeof(double), hipMemcpyDeviceToHost));
-   if (a.ypred) HIP_CHECK(hipMemcpy(a.ypred, d_ypred, (size_t)ncols * N * sizeof(double), hipMemcpyDeviceToHost));
+   if (a.xpred) HIP_CHECK(hipMemcpy(a.xpred, d_xpred.p, (size_t)ncols * N * sizeof(double), hipMemcpyDeviceToHost));
+   if (a.ypred) HIP_CHECK(hipMemcpy(a.ypred, d_ypred.p, (size_t)ncols * N * sizeof(double), hipMemcpyDeviceToHost));
    if (timing)
       std::fprintf(stderr,
                    "[fpca] scca_cv: fold counts %.3f ms, per-fold setup %.3f ms, K2 %.3f ms, fits %.3f ms (%ld iterations), K3 + gather %.3f ms, "
@@ -614,17 +580,16 @@ extern "C" int fpca_debug_fold_stats(fpca_ctx *ctx, const uint8_t *fold, int nfo
       std::vector<uint8_t> masks;
       std::vector<uint64_t> fsize;
       build_masks(fold, ctx->N, nfolds, ctx->pitch, masks, fsize);
-      DevBufs bufs;
       static const char *FN = "fpca_debug_fold_stats";
-      uint8_t *d_masks = bufs.get<uint8_t>(masks.size(), FN, "the fold masks");
-      uint32_t *d_counts = bufs.get<uint32_t>((size_t)nfolds * P * 3, FN, "the per-fold genotype counts");
-      double *d_ms = bufs.get<double>(2 * (size_t)P, FN, "mean / sd");
-      HIP_CHECK(hipMemcpyAsync(d_masks, masks.data(), masks.size(), hipMemcpyHostToDevice, s));
-      launch_fold_counts(ctx, d_masks, nfolds, d_counts, s);
-      if (counts && P) HIP_CHECK(hipMemcpyAsync(counts, d_counts, (size_t)nfolds * P * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      DevMem<uint8_t> d_masks(masks.size(), FN, "the fold masks", 8);
+      DevMem<uint32_t> d_counts((size_t)nfolds * P * 3, FN, "the per-fold genotype counts", 8);
+      DevMem<double> d_ms(2 * (size_t)P, FN, "mean / sd", 8);
+      HIP_CHECK(hipMemcpyAsync(d_masks.p, masks.data(), masks.size(), hipMemcpyHostToDevice, s));
+      launch_fold_counts(ctx, d_masks.p, nfolds, d_counts.p, s);
+      if (counts && P) HIP_CHECK(hipMemcpyAsync(counts, d_counts.p, (size_t)nfolds * P * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
       if (mean_sd && P) {
-         launch_fold_meansd(ctx, d_counts, nfolds, which_fold, d_ms, d_ms + P, s);
-         HIP_CHECK(hipMemcpyAsync(mean_sd, d_ms, 2 * (size_t)P * sizeof(double), hipMemcpyDeviceToHost, s));
+         launch_fold_meansd(ctx, d_counts.p, nfolds, which_fold, d_ms.p, d_ms.p + P, s);
+         HIP_CHECK(hipMemcpyAsync(mean_sd, d_ms.p, 2 * (size_t)P * sizeof(double), hipMemcpyDeviceToHost, s));
       }
       HIP_CHECK(hipStreamSynchronize(s));
    });

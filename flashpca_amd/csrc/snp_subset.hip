@@ -157,7 +157,6 @@ extern "C" int fpca_create_snp_subset(fpca_ctx **out, fpca_ctx *src, const uint8
 {
    if (out) *out = nullptr;
    fpca_ctx *c = nullptr;
-   uint32_t *d_idx = nullptr;
    int rc = guarded([&] {
       if (!out || !src || !keep)
          throw Error(FPCA_EINVAL, std::string("bad argument to fpca_create_snp_subset (") + (!out ? "out" : !src ? "src" : "keep") + " is NULL)");
@@ -187,12 +186,11 @@ extern "C" int fpca_create_snp_subset(fpca_ctx **out, fpca_ctx *src, const uint8
          throw Error(FPCA_ENOMEM, msg);
       }
       HIP_CHECK(hipStreamSynchronize(src->stream)); // (nothing writes the source's matrix after its upload; its stream may still read it)
-      HIP_ALLOC(hipMalloc(&d_idx, idx.size() * sizeof(uint32_t)));
-      HIP_CHECK(hipMemcpyAsync(d_idx, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-      kern::gather_records(src->d_packed, src->pitch, d_idx, idx.size(), c->d_packed, c->stream); // (behind the 0x55 memset, same stream)
+      DevMem<uint32_t> d_idx(idx.size(), "fpca_create_snp_subset", "the list of the kept SNPs");
+      HIP_CHECK(hipMemcpyAsync(d_idx.p, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+      kern::gather_records(src->d_packed, src->pitch, d_idx.p, idx.size(), c->d_packed, c->stream); // (behind the 0x55 memset, same stream)
       HIP_CHECK(hipStreamSynchronize(c->stream));
    });
-   if (d_idx) (void)hipFree(d_idx);
    if (rc != FPCA_OK) {
       if (c) ctx_free(c);
       return rc;

@@ -68,21 +68,6 @@ __global__ __launch_bounds__(64) void k_ucca_finish(const double *__restrict__ n
    res[2 * P_g + j] = P;
 }
 
-// device scratch of one call, released on every way out
-struct DevBuf {
-   double *p = nullptr;
-   explicit DevBuf(size_t n)
-   {
-      if (n) HIP_ALLOC(hipMalloc(&p, n * sizeof(double)));
-   }
-   ~DevBuf()
-   {
-      if (p) (void)hipFree(p);
-   }
-   DevBuf(const DevBuf &) = delete;
-   DevBuf &operator=(const DevBuf &) = delete;
-};
-
 // Householder QR of the N x k column-major A (overwritten): the diagonal and upper triangle of R, k x k column-major
 void householder_r(double *A, uint64_t N, int k, std::vector<double> &R)
 {
@@ -125,7 +110,7 @@ void ucca(fpca_ctx *c, const double *Y, int64_t ldy, int k, int stand_y, double 
    // 1. phenotypes: upload as rows of a [k][N_pad] image, standardise there (util.cpp:24-110), download the standardised N x k
    std::vector<double> Ys((size_t)N * k);
    {
-      DevBuf dY((size_t)k * c->N_pad), dstat(3 * (size_t)k);
+      DevMem<double> dY((size_t)k * c->N_pad, "fpca_ucca", "the phenotypes"), dstat(3 * (size_t)k, "fpca_ucca", "the phenotype statistics");
       HIP_CHECK(hipMemcpy2DAsync(dY.p, c->N_pad * sizeof(double), Y, (size_t)ldy * sizeof(double), N * sizeof(double), k, hipMemcpyHostToDevice, s));
       kern::dense_standardise(dY.p, c->N_pad, N, k, stand_y, dstat.p, dstat.p + k, dstat.p + 2 * k, s);
       HIP_CHECK(hipMemcpy2DAsync(Ys.data(), N * sizeof(double), dY.p, c->N_pad * sizeof(double), N * sizeof(double), k, hipMemcpyDeviceToHost, s));
@@ -133,16 +118,7 @@ void ucca(fpca_ctx *c, const double *Y, int64_t ldy, int k, int stand_y, double 
    }
    // column means of the standardised Y (blocked sums)
    std::vector<double> ybar(k);
-   for (int j = 0; j < k; j++) {
-      const double *y = Ys.data() + (size_t)j * N;
-      double tot = 0;
-      for (uint64_t i0 = 0; i0 < N; i0 += 1024) {
-         double sb = 0;
-         for (uint64_t i = i0; i < std::min<uint64_t>(N, i0 + 1024); i++) sb += y[i];
-         tot += sb;
-      }
-      ybar[j] = tot / (double)N;
-   }
+   for (int j = 0; j < k; j++) ybar[j] = blocked_sum(Ys.data() + (size_t)j * N, N) / (double)N;
 
    // 2. R of the thin QR of Y (on a copy: Ys is needed again for Y_c)
    std::vector<double> R;
@@ -176,7 +152,7 @@ void ucca(fpca_ctx *c, const double *Y, int64_t ldy, int k, int stand_y, double 
 
    // 4. the chunked K2 pass X_g' B, the numerator accumulated after each chunk, then the statistics
    ensure_io(c);
-   DevBuf dnum(c->P_pad), dsumx(c->P_pad), dres(3 * P);
+   DevMem<double> dnum(c->P_pad, "fpca_ucca", "the numerators"), dsumx(c->P_pad, "fpca_ucca", "the column sums"), dres(3 * P, "fpca_ucca", "the statistics");
    for (int c0 = 0; c0 < ncol; c0 += MAX_BLOCKVEC) {
       const int nc = std::min(MAX_BLOCKVEC, ncol - c0), bw = pad16(nc);
       const int ncw = std::max(0, std::min(k, c0 + nc) - c0), ones_col = (k < c0 + nc) ? k - c0 : -1;

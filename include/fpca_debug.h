@@ -145,6 +145,16 @@ int fpca_debug_king_rule(const uint32_t *i, const uint32_t *j, uint64_t n_pairs,
  * 32 per MFMA, pad SNPs included). */
 int fpca_bench_king(fpca_ctx *ctx, int reps, double *ms, double *macs);
 
+/* diagnostic (tests/test_gpu_scratch.py), builds with -DFPCA_TEST_HOOKS only: what the entry points hold for the length of one call --
+ * device memory, pinned host memory, events (csrc/dev_scratch.hpp) -- is counted, and one acquisition can be made to fail.
+ *   fpca_debug_scratch_live     out[0..2] = live device allocations, pinned allocations, events made through those owners: equal before
+ *                               and after a call that leaks nothing, whichever way it ends.
+ *   fpca_debug_scratch_fail_at  the n-th acquisition from now (1 = the next; allocation or event alike) throws FPCA_ENOMEM as if the
+ *                               device were full, before the runtime is asked for anything; the countdown then disarms.  n = 0 disarms.
+ * In the product build both return FPCA_EINVAL with a message that says so and do nothing: no switch changes what it computes. */
+int fpca_debug_scratch_live(uint64_t out[3]);
+int fpca_debug_scratch_fail_at(uint64_t n);
+
 #ifdef __cplusplus
 }
 #endif
