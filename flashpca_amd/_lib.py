@@ -127,6 +127,11 @@ SIGNATURES = {
     "fpca_king_block": (_I, [_P, _U64, _U64, _U64, _U64, _P]),
     "fpca_king_pairs": (_I, [_P, _P, _D, _U64, _P, _P, _P, C.POINTER(_U64)]),
     "fpca_king_cutoff": (_I, [_P, _D, _P, C.POINTER(_U64)]),
+    "fpca_snp_counts": (_I, [_P, _P, _P]),
+    "fpca_sample_counts": (_I, [_P, _P, _P]),
+    "fpca_hwe_exact": (_I, [_P, _P, _U64, _P]),
+    "fpca_sample_qc": (_I, [_P, _P, _D, _P, C.POINTER(_U64)]),
+    "fpca_snp_qc_samples": (_I, [_P, _P, _D, _D, _D, _P, C.POINTER(_U64)]),
     "fpca_apply_xxt": (_I, [_P, _P, C.c_int64, _I, _P, C.c_int64]),
     "fpca_apply_xt": (_I, [_P, _P, C.c_int64, _I, _P, C.c_int64]),
     "fpca_apply_x": (_I, [_P, _P, C.c_int64, _I, _P, C.c_int64]),
@@ -176,6 +181,9 @@ SIGNATURES = {
     "fpca_bench_ld": (_I, [_P, C.c_uint32, _I, _P, C.POINTER(_D)]),
     "fpca_debug_king_rule": (_I, [_P, _P, _U64, _U64, _P, C.POINTER(_U64)]),
     "fpca_bench_king": (_I, [_P, _I, _P, C.POINTER(_D)]),
+    "fpca_debug_sample_qc_rule": (_I, [_P, _U64, _U64, _D, _P, C.POINTER(_U64)]),
+    "fpca_debug_snp_qc_counts_rule": (_I, [_P, _P, _U64, _U64, _D, _D, _D, _P, C.POINTER(_U64)]),
+    "fpca_bench_qc": (_I, [_P, _I, _P, C.POINTER(_D)]),
     "fpca_debug_scratch_live": (_I, [C.POINTER(_U64)]),
     "fpca_debug_scratch_fail_at": (_I, [_U64]),
 }

@@ -291,6 +291,67 @@ class Context:
         check(lib().fpca_bench_king(self.h, int(reps), _p(ms), C.byref(macs)))
         return ms, macs.value
 
+    # ---- genotype census ------------------------------------------------------------------------------
+    def snp_counts(self, samples=None):
+        """fpca_snp_counts: the P x 4 uint32 array of genotype counts per SNP by raw .bed code (0 homozygous A1, 1 missing, 2 heterozygous,
+        3 homozygous A2) over the samples of `samples` (a boolean array with one entry per sample; None: all)."""
+        out = np.empty((self.P, 4), dtype=np.uint32)
+        check(lib().fpca_snp_counts(self.h, _p(self._sample_keep(samples)), _p(out)))
+        return out
+
+    def sample_counts(self, snps=None):
+        """fpca_sample_counts: the N x 4 uint32 array of genotype counts per sample by raw .bed code over the SNPs of `snps` (a mask or an
+        index array; None: all)."""
+        s8 = None if snps is None else np.ascontiguousarray(_snp_mask(snps, self.P), dtype=np.uint8)
+        out = np.empty((self.N, 4), dtype=np.uint32)
+        check(lib().fpca_sample_counts(self.h, _p(s8), _p(out)))
+        return out
+
+    def hwe_exact(self, counts):
+        """fpca_hwe_exact: the Hardy-Weinberg exact-test p-value (Wigginton, Cutler & Abecasis 2005; no mid-p) of every row of `counts`,
+        an n x 4 array of non-negative integers by raw code as snp_counts() returns it (column 1, the missing calls, is not read)."""
+        c = np.asarray(counts)
+        if c.ndim != 2 or c.shape[1] != 4 or not (c.size == 0 or np.issubdtype(c.dtype, np.integer)):
+            raise ValueError("counts is an n x 4 array of integers (hom A1, missing, het, hom A2), found shape %s" % (c.shape,))
+        if c.size and (c.min() < 0 or c.max() >= 2 ** 32):
+            raise ValueError("counts must be in 0 .. 2^32 - 1")
+        c32 = np.ascontiguousarray(c, dtype=np.uint32)
+        out = np.empty(c32.shape[0], dtype=np.float64)
+        check(lib().fpca_hwe_exact(self.h, _p(c32), c32.shape[0], _p(out)))
+        return out
+
+    def sample_qc(self, mind, snps=None, keep=None):
+        """fpca_sample_qc: the boolean mask of the samples whose missing-call rate over the SNPs of `snps` (a mask or an index array; None:
+        all) is <= mind (PLINK's --mind; mind >= 1 switches the filter off), among those of `keep` (one entry per sample; None: all)."""
+        s8 = None if snps is None else np.ascontiguousarray(_snp_mask(snps, self.P), dtype=np.uint8)
+        k8 = self._sample_keep(keep)
+        if k8 is None:
+            k8 = np.ones(self.N, dtype=np.uint8)
+        n = C.c_uint64(0)
+        check(lib().fpca_sample_qc(self.h, _p(s8), float(mind), _p(k8), C.byref(n)))
+        out = k8 != 0
+        assert int(out.sum()) == n.value
+        return out
+
+    def snp_qc_samples(self, samples, maf=0.0, geno=1.0, hwe=0.0, keep=None):
+        """fpca_snp_qc_samples: the boolean mask of the SNPs with minor-allele frequency >= maf, missing-call rate <= geno and HWE exact-test
+        p-value >= hwe (PLINK's --maf / --geno / --hwe; maf <= 0, geno >= 1 and hwe <= 0 switch a filter off), all three taken over the
+        samples of `samples` (one entry per sample; None: all), among the SNPs of `keep` (a mask or an index array; None: all)."""
+        k8 = np.ascontiguousarray(np.ones(self.P, dtype=bool) if keep is None else _snp_mask(keep, self.P), dtype=np.uint8)
+        n = C.c_uint64(0)
+        check(lib().fpca_snp_qc_samples(self.h, _p(self._sample_keep(samples)), float(maf), float(geno), float(hwe), _p(k8), C.byref(n)))
+        out = k8 != 0
+        assert int(out.sum()) == n.value
+        return out
+
+    def bench_qc(self, reps=5):
+        """fpca_bench_qc: (milliseconds per launch of the per-SNP count pass, of the per-sample count pass and of the HWE kernel; the
+        recurrence steps one HWE launch makes at most)."""
+        ms = np.zeros(3, dtype=np.float64)
+        steps = C.c_double(0)
+        check(lib().fpca_bench_qc(self.h, int(reps), _p(ms), C.byref(steps)))
+        return ms, steps.value
+
     def set_total_snps(self, P_total):
         check(lib().fpca_set_total_snps(self.h, int(P_total)))
         self.P_total = int(P_total)
@@ -582,7 +643,7 @@ def debug_gather(ptr, idx, V, b, rows_out=None, rowscale=None, colw=None, init=N
 
 def flashpca(X, ndim=10, stand="binom2", divisor="p", maxiter=500, tol=1e-6, do_loadings=False, return_scale=True,
              device=0, verbose=False, accum="auto", keep=None, snps=None, maf=0.0, geno=1.0, ld=None, unrelated=None,
-             **solver_kw):
+             mind=1.0, hwe=0.0, **solver_kw):
     """PCA of a PLINK fileset; mirrors flashpca() of the reference's R package for the PLINK-prefix input
     (flashpcaR/R/flashpca.R:99-204 -> flashpca_plink_internal, flashpcaR/src/flashpca.cpp:96-197).
 
@@ -601,16 +662,28 @@ def flashpca(X, ndim=10, stand="binom2", divisor="p", maxiter=500, tol=1e-6, do_
     stay over all samples, the usual QC-then-KING order, and are allowed with it as long as keep is None -- Context.king_cutoff on the
     selected SNPs picks the samples (among those of keep=, if given), and the PCA runs on them as under keep=: the result gains
     `unrelated_kept`, the mask over the samples, and `projection_all`.
+    mind / hwe: PLINK's --mind (missing-call rate per sample <= mind) and --hwe (Hardy-Weinberg exact-test p-value per SNP >= hwe; no
+    mid-p).  PLINK input only.  With either of them the order is: the snps list; mind, whose rate is over the listed SNPs and all samples
+    (among the samples of keep=, if given); geno / hwe / maf over the samples mind left (Context.snp_qc_samples); ld, whose r2 stays over
+    all samples; unrelated among the samples left; the PCA on those samples as under keep=.  With mind the result gains `mind_kept`, the
+    mask over the samples, and `projection_all`.  keep= goes with mind=, not with hwe= (nor maf / geno): for frequencies over a
+    hand-picked subset of the samples take the masks from qc_filter(..., keep=) and pass them as snps= and keep=.
     Returns values, vectors, projection, loadings, center, scale, pve.
     """
     if divisor not in DIVISOR:
         raise ValueError("divisor must be one of %s" % sorted(DIVISOR))
     qc = not (maf <= 0 and geno >= 1)  # (a NaN threshold counts as a filter: fpca_snp_qc refuses it)
+    by_mind, by_hwe = not mind >= 1, not hwe <= 0  # (a NaN threshold counts as a filter here too)
     if (snps is not None or qc) and not isinstance(X, str):
         raise ValueError("snps / maf / geno select SNPs of a PLINK fileset; they do not apply to a numeric matrix")
+    if (by_mind or by_hwe) and not isinstance(X, str):
+        raise ValueError("mind / hwe filter the samples / SNPs of a PLINK fileset; they do not apply to a numeric matrix")
     if qc and keep is not None:
         raise ValueError("maf / geno cannot be combined with keep: PLINK takes these frequencies over the kept samples, the counts here "
                          "are those of all samples")
+    if by_hwe and keep is not None:
+        raise ValueError("hwe cannot be combined with keep: flashpca() takes the genotype counts over the samples mind= leaves; for a "
+                         "hand-picked subset take the masks from qc_filter(..., keep=) and pass them as snps= and keep=")
     if ld is not None:
         ld = _ld_args(ld)
         if not isinstance(X, str):
@@ -630,8 +703,26 @@ def flashpca(X, ndim=10, stand="binom2", divisor="p", maxiter=500, tol=1e-6, do_
         if stand not in _lib.STANDARDISE_DENSE:
             raise ValueError("stand must be one of %s" % sorted(_lib.STANDARDISE_DENSE))
         ctx = Context.from_dense(np.asarray(X, dtype=np.float64), stand=stand, device=device)
-    snps_kept = None
-    if snps is not None or qc or ld is not None:
+    snps_kept = mind_kept = None
+    if by_mind or by_hwe:
+        select = snps is not None or qc or by_hwe or ld is not None
+        full = ctx
+        try:
+            mind_kept, mask = _qc_masks(full, X, snps, mind, maf, geno, hwe, ld, keep)
+            if not by_mind:
+                mind_kept = None
+            elif int(mind_kept.sum()) < 2:
+                raise ValueError("mind = %g leaves %d of %d samples; at least 2 are needed" % (mind, int(mind_kept.sum()), full.N))
+            else:
+                keep = mind_kept
+            if select:  # (mind alone drops no SNP: the PCA runs on the uploaded matrix itself)
+                ctx, snps_kept = full.snp_subset(mask), mask
+        except BaseException:
+            full.close()
+            raise
+        if ctx is not full:
+            full.close()
+    elif snps is not None or qc or ld is not None:
         with ctx as full:  # (the source is closed on the way out)
             ctx, snps_kept = _select_snps(full, X, snps, qc, maf, geno, ld)
     with ctx:
@@ -652,6 +743,8 @@ def flashpca(X, ndim=10, stand="binom2", divisor="p", maxiter=500, tol=1e-6, do_
         res.update(vectors=r["U"][keep], projection=r["Px"][keep], projection_all=r["Px"])
     if unrelated_kept is not None:
         res["unrelated_kept"] = unrelated_kept
+    if mind_kept is not None:
+        res["mind_kept"] = mind_kept
     if snps_kept is not None:
         res["snps_kept"] = snps_kept
     if return_scale:
@@ -1052,12 +1145,18 @@ def _selection_mask(full, prefix, snps, qc, maf, geno, ld):
     mask = np.ones(full.P, dtype=bool) if snps is None else _snp_mask(snps, full.P)
     if qc:
         mask = full.snp_qc(maf=maf, geno=geno, keep=mask)
+    return _ld_survivors(full, prefix, mask, ld, snps is None and not qc)
+
+
+def _ld_survivors(full, prefix, mask, ld, untouched):
+    """LD pruning (ld: (window, step, r2) or None) of the SNPs of `mask` on the uploaded fileset `full`; untouched: nothing was filtered
+    before, the mask is all ones."""
     if ld is None:
         return mask
     chrom = _bim_chrom_codes(prefix)
     if chrom.shape != (full.P,):
         raise ValueError("%s.bim has %d rows, the .bed holds %d SNPs" % (prefix, chrom.size, full.P))
-    if snps is None and not qc:  # nothing filtered before: the windows count the fileset's own SNPs, no first compaction
+    if untouched:  # nothing filtered before: the windows count the fileset's own SNPs, no first compaction
         return full.ld_prune(*ld, chrom=chrom)
     # the windows count the survivors of the earlier filters, as in PLINK: prune on their compaction (gone again before the caller
     # compacts the final mask from the source: a gather of a gather is a gather)
@@ -1066,6 +1165,29 @@ def _selection_mask(full, prefix, snps, qc, maf, geno, ld):
     mask = mask.copy()
     mask[np.flatnonzero(mask)] = kept
     return mask
+
+
+def _qc_masks(full, prefix, snps, mind, maf, geno, hwe, ld, keep):
+    """(sample mask, SNP mask) of flashpca()'s QC order on the uploaded fileset `full`: the snps list; mind over the listed SNPs among the
+    samples of keep; geno / hwe / maf over the samples left; LD pruning of the surviving SNPs, its r2 over all samples."""
+    mask = np.ones(full.P, dtype=bool) if snps is None else _snp_mask(snps, full.P)
+    samples = full.sample_qc(mind, snps=mask, keep=keep)  # (mind >= 1: keep itself, or everyone)
+    if not (maf <= 0 and geno >= 1 and hwe <= 0):
+        mask = full.snp_qc_samples(samples, maf=maf, geno=geno, hwe=hwe, keep=mask)
+    return samples, _ld_survivors(full, prefix, mask, ld, False)
+
+
+def qc_filter(prefix, mind=1.0, geno=1.0, hwe=0.0, maf=0.0, snps=None, keep=None, device=0):
+    """The four QC filters the reference's README asks for before a PCA, on the GPU: (sample_mask, snp_mask), boolean masks over the rows of
+    prefix.fam and prefix.bim, in the manner of `plink --mind mind --geno geno --hwe hwe --maf maf` and in flashpca()'s order: the snps
+    list (a mask or an index array); mind, the missing-call rate per sample over the listed SNPs, among the samples of keep (a boolean
+    array with one entry per sample; None: all); then geno, hwe and maf per SNP over the samples left.  Unlike flashpca(), keep= goes
+    with every filter: qc_filter(..., keep=) followed by flashpca(prefix, snps=snp_mask, keep=sample_mask) is the route when the
+    frequencies of a hand-picked subset of the samples are wanted.  hwe is the exact test without mid-p, over all the samples counted
+    (no founders-only or controls-only counting); not byte-compatible with the plink binary."""
+    N = count_fam_rows(prefix + ".fam")
+    with Context.from_bed(prefix + ".bed", N, device=device, accum="fp64") as full:
+        return _qc_masks(full, prefix, snps, mind, maf, geno, hwe, None, keep)
 
 
 def _select_snps(full, prefix, snps, qc, maf, geno, ld):

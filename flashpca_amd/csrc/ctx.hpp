@@ -24,6 +24,9 @@
 //                       (k_ld_band, six exact int8 products per pair), the --indep-pairwise rule on the host
 //   king.hip            fpca_king_block / fpca_king_pairs / fpca_king_cutoff: KING-robust kinship as the same Gram on a sample-major copy
 //                       (k_king, five products per pair; the loop itself is ld_planes.hpp), the greedy unrelated-sample rule on the host
+//   qc_census.hip       fpca_snp_counts / fpca_sample_counts / fpca_hwe_exact / fpca_sample_qc / fpca_snp_qc_samples: genotype counts per SNP
+//                       over chosen samples (k_snp_counts) and per sample over chosen SNPs (k_sample_counts, a column census with vertical
+//                       counters), the HWE exact test (k_hwe_exact, one SNP per lane), the --mind and --geno / --maf / --hwe rules on the host
 // MI355X / gfx950 only; there is no CPU fallback anywhere in the library.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -341,6 +344,14 @@ void ld_check_window(const char *fn, uint32_t window, uint32_t step); // FPCA_EI
 // n_pairs, all below N; while an edge remains the sample of largest current degree goes, the largest index among equals.  keep[N] in and
 // out (entries become 0 / 1, a 0 stays 0); returns the number left non-zero.
 uint64_t king_cutoff_rule(const uint32_t *i, const uint32_t *j, uint64_t n_pairs, uint64_t N, uint8_t *keep);
+
+// ---- qc_census.hip ----------------------------------------------------------------------------------------
+// host only: the rules of fpca_sample_qc / fpca_snp_qc_samples (include/fpca.h) on counts by raw code ([.][4]: hom A1, missing, het, hom A2).
+// samples[N] / keep[P] in and out (entries become 0 / 1, a 0 stays 0); both return the number left non-zero.  n_snps and n are not 0.
+uint64_t sample_qc_rule(const uint32_t *counts, uint64_t n_snps, uint64_t N, double max_missing, uint8_t *samples);
+// p_hwe[P] is read only when min_hwe_p > 0; n: the samples the counts were taken over
+uint64_t snp_qc_counts_rule(const uint32_t *counts, const double *p_hwe, uint64_t n, uint64_t P, double min_maf, double max_missing, double min_hwe_p,
+                            uint8_t *keep);
 
 // ---- download.hip -----------------------------------------------------------------------------------------
 // d_img: device, column-major N x ncols with leading dimension N -> host (ld) and, scaled per column, host2 (ld2); synchronises

@@ -257,6 +257,50 @@ int fpca_king_pairs(fpca_ctx *ctx, const uint8_t *keep /* [N] or NULL */, double
                     uint64_t *n_pairs);
 int fpca_king_cutoff(fpca_ctx *ctx, double thr, uint8_t *keep /* [N] in/out, like fpca_snp_qc */, uint64_t *n_kept);
 
+/* Genotype census: counts per SNP over a chosen set of samples, counts per sample over a chosen set of SNPs, the Hardy-Weinberg exact test
+ * on such counts, and the two QC rules on top of them -- PLINK's --mind (per-sample call rate) and --geno / --maf / --hwe over the KEPT
+ * samples.  The masks they leave feed fpca_set_sample_mask and fpca_create_snp_subset.
+ *   Raw codes.  Every count is indexed by the raw .bed code c: 0 homozygous A1 (dosage 2), 1 missing, 2 heterozygous, 3 homozygous A2
+ *   (dosage 0).  Pad cells (samples >= N, records >= P_g) are never counted.
+ *   fpca_snp_counts      counts[j][c], j < P_g: over the samples i < N with samples[i] != 0 (NULL: all).
+ *   fpca_sample_counts   counts[i][c], i < N: over the SNPs j < P_g with snps[j] != 0 (NULL: all).  Slabs of SNPs are combined with integer
+ *                        adds, so a repeat call is bit-identical.
+ *   fpca_sample_qc       samples[N] in and out, as for fpca_snp_qc: an entry that is 0 stays 0; *n_kept (may be NULL) = entries left
+ *                        non-zero.  n_snps = the SNPs counted (snps as above), miss_i = (double)counts[i][1] / (double)n_snps over ALL of
+ *                        them whatever samples[] holds; sample i is dropped when miss_i > max_missing (strict: a sample exactly at the
+ *                        threshold stays).  max_missing >= 1 disables the filter.  FPCA_EINVAL when n_snps == 0, max_missing is NaN or < 0.
+ *   fpca_snp_qc_samples  snps[P_g] in and out likewise.  Counts over the samples with samples[i] != 0 (NULL: all), n of them;
+ *                        ngood = cnt[0] + cnt[2] + cnt[3].
+ *                           geno: dropped when (double)cnt[1] / (double)n > max_missing                     (max_missing >= 1: off)
+ *                           maf:  mean = (double)(2 cnt[0] + cnt[2]) / (double)ngood, p = mean / 2, maf = ngood == 0 ? 0 : min(p, 1 - p);
+ *                                 dropped when maf < min_maf -- K1's arithmetic: with all samples the decision is fpca_snp_qc's, bit for
+ *                                 bit                                                                        (min_maf <= 0: off)
+ *                           hwe:  dropped when p_hwe < min_hwe_p (strict), p_hwe as below                    (min_hwe_p <= 0: off)
+ *                        FPCA_EINVAL for the thresholds fpca_snp_qc refuses, min_hwe_p NaN or above 1, and a mask that keeps no sample.
+ *   fpca_hwe_exact       p[k], k < n, from counts[k][4] as above (column 1 is not read): the exact test of Wigginton, Cutler & Abecasis
+ *                        (2005), without their array.
+ *                           a = cnt[2], b = min(cnt[0], cnt[3]), c = max(cnt[0], cnt[3]), n = a + b + c, r = 2 b + a        (n == 0: p = 1)
+ *                           the possible heterozygote counts are h = r, r - 2, ... >= 0
+ *                           mid = floor(r (2n - r) / (2n)) in integers, plus 1 when its parity differs from r's;  w(mid) = 1
+ *                           with hr = (r - h) / 2, hc = n - h - hr:
+ *                              downwards  w(h - 2) = w(h) * (h (h - 1)) / (4 (hr + 1) (hc + 1))
+ *                              upwards    w(h + 2) = w(h) * (4 hr hc) / ((h + 2) (h + 1))
+ *                           (the integer factors are exact in fp64 for n < 2^26; ONE multiply and ONE divide are rounded per step, no FMA)
+ *                           p = min(1, sum{ w(h) : w(h) <= w(a) (1 + 2^-20) } / sum w(h))
+ *                        The factor 1 + 2^-20 makes exact ties (mirror-image terms) count whatever the rounding does.  A walk stops at a
+ *                        term that is exactly 0.0 (every later one is 0 too); there is no other truncation.  w(a) == 0 through underflow
+ *                        gives p = 0.  On the device, one SNP per lane.
+ *   Not claimed: the mid-p variant; founders-only or controls-only counting; byte parity with the plink binary.
+ *   All five: FPCA_EINVAL, before any device work, for a NULL argument (a mask documented as "NULL: all" excepted), a dense context, one
+ *   shard of several, a context under a sample mask (clear it and pass the mask as `samples`), N or P_g >= 2^32.  A preloaded mean/sd is
+ *   not refused: nothing here reads it.  The context is not changed. */
+int fpca_snp_counts(fpca_ctx *ctx, const uint8_t *samples /* [N] or NULL */, uint32_t *counts /* [P_g][4] */);
+int fpca_sample_counts(fpca_ctx *ctx, const uint8_t *snps /* [P_g] or NULL */, uint32_t *counts /* [N][4] */);
+int fpca_hwe_exact(fpca_ctx *ctx, const uint32_t *counts /* [n][4] */, uint64_t n, double *p /* [n] */);
+int fpca_sample_qc(fpca_ctx *ctx, const uint8_t *snps /* [P_g] or NULL */, double max_missing, uint8_t *samples /* [N] in/out */, uint64_t *n_kept);
+int fpca_snp_qc_samples(fpca_ctx *ctx, const uint8_t *samples /* [N] or NULL */, double min_maf, double max_missing, double min_hwe_p,
+                        uint8_t *snps /* [P_g] in/out */, uint64_t *n_kept);
+
 /* ------------------------------------------------------------------------------------------------
  * Operator.  b columns at a time; b = 1 is exactly the reference's perform_op.
  *   fpca_apply_xxt : Y = X_g X_g' B        replaces SVDWideOnline::perform_op / perform_op_mat

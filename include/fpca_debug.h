@@ -144,6 +144,18 @@ int fpca_debug_king_rule(const uint32_t *i, const uint32_t *j, uint64_t n_pairs,
  * triangle) with a pair of HIP events around each, ms[reps].  *macs (may be NULL): int8 multiply-accumulates one pass issues (32 x 32 x
  * 32 per MFMA, pad SNPs included). */
 int fpca_bench_king(fpca_ctx *ctx, int reps, double *ms, double *macs);
+/* diagnostic (tests): the rules of fpca_sample_qc / fpca_snp_qc_samples on caller arrays, no context and no device involved.  counts:
+ * uint32 [N][4] / [P][4] by raw code; n_snps: the SNPs the per-sample counts were taken over; n: the samples the per-SNP counts were taken
+ * over; p_hwe[P]: the p-values, read only when min_hwe_p > 0 (may be NULL otherwise); samples[N] / keep[P] in and out.  FPCA_EINVAL for
+ * the thresholds the entry points refuse, n_snps == 0 and n == 0. */
+int fpca_debug_sample_qc_rule(const uint32_t *counts, uint64_t n_snps, uint64_t N, double max_missing, uint8_t *samples, uint64_t *n_kept);
+int fpca_debug_snp_qc_counts_rule(const uint32_t *counts, const double *p_hwe, uint64_t n, uint64_t P, double min_maf, double max_missing,
+                                  double min_hwe_p, uint8_t *keep, uint64_t *n_kept);
+/* time the three kernels of the genotype census alone (scripts/qc_measure.py), all samples and all SNPs: scratch is ready before the clock
+ * starts; one untimed launch, then `reps` timed ones.  ms[3]: milliseconds per launch of the per-SNP count pass, of the per-sample count
+ * pass (with the clear of its count planes) and of the HWE kernel on the counts of the first.  *hwe_steps (may be NULL): recurrence steps
+ * one HWE launch makes at most. */
+int fpca_bench_qc(fpca_ctx *ctx, int reps, double *ms, double *hwe_steps);
 
 /* diagnostic (tests/test_gpu_scratch.py), builds with -DFPCA_TEST_HOOKS only: what the entry points hold for the length of one call --
  * device memory, pinned host memory, events (csrc/dev_scratch.hpp) -- is counted, and one acquisition can be made to fail.
