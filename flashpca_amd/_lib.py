@@ -94,6 +94,10 @@ class BenchResult(C.Structure):
     ]
 
 
+class SlicesOut(C.Structure):  # fpca_debug_slices_out: host buffers of one operand, NULL = not wanted
+    _fields_ = [(n, C.c_void_p) for n in ("colmax", "maxbits_own", "maxbits", "Q", "Qrm", "colw", "colsum", "copy32", "copy64", "dq32", "dq64")]
+
+
 # every function include/fpca.h declares: name -> (restype, argtypes)
 _P, _U64, _I, _D = C.c_void_p, C.c_uint64, C.c_int, C.c_double
 SIGNATURES = {
@@ -173,6 +177,8 @@ SIGNATURES = {
     "fpca_debug_poison_partials": (_I, [_P]),
     "fpca_debug_missing_lists": (_I, [_P, _I, _I, _P, _P, _U64, C.POINTER(_U64)]),
     "fpca_debug_gather": (_I, [_I, _I, _P, _P, _U64, _P, _U64, _P, _P, _P, _U64, _U64, _I, _D, _P, C.POINTER(_I)]),
+    "fpca_debug_i8_nsc_pad": (_I, [_I, _I, C.POINTER(_I)]),
+    "fpca_debug_i8_slices": (_I, [_I, _I, _I, _U64, _U64, _U64, _P, _P, _P, _P, _I, C.POINTER(SlicesOut), C.POINTER(SlicesOut), C.POINTER(_I)]),
     "fpca_debug_f_sf":(_I, [_D, _U64, _I, C.POINTER(_D), C.POINTER(_D)]),
     "fpca_debug_fold_stats": (_I, [_P, _P, _I, _P, _I, _P]),
     "fpca_debug_snp_qc_rule": (_I, [_P, _P, _U64, _U64, _D, _D, _P, C.POINTER(_U64)]),

@@ -641,6 +641,58 @@ def debug_gather(ptr, idx, V, b, rows_out=None, rowscale=None, colw=None, init=N
     return out[:rows_out], variant.value
 
 
+def debug_i8_slices(V, b, S, rows=None, route=0, rowscales=(), peers=None, rows_valid=0, colsum=(True, True), copy=(None, None), dequant=()):
+    """fpca_debug_i8_slices: the int8 slicing kernels on caller data.  V: rows_pad x b fp64, of which `rows` rows count (default all); route 0:
+    the operator's own slicing (i8_colmax, i8_slice), route 1: the row-sharded exchange (i8_slice_rows, i8_unpack_slices, i8_dequant_rows);
+    rowscales: 0, 1 or 2 vectors of `rows` factors (2: two operands from one pass, route 0); peers: G-1 x 64 maxima of other ranks;
+    colsum[o]: ask operand o for its column sums; copy[o]: None, 32 or 64, the copy of the scaled operand the slicing pass leaves;
+    dequant: which of (32, 64) i8_dequant_rows is run for (route 1).  Returns one dict per operand: colmax [64], maxbits_own and maxbits
+    [8][64] uint64, Q [nsc_pad][rows_pad] int8, colw [nsc_pad], nsc_pad, and where asked for colsum [640] int64 (the shards summed) with
+    colsum_shards [8][640], copy32 / copy64 [rows_pad][b], and on route 1 Qrm [rows_pad][S b], dq32 / dq64."""
+    V = np.ascontiguousarray(V, dtype=np.float64)
+    if V.ndim != 2 or V.shape[1] != b:
+        raise ValueError("V is rows_pad x b")
+    rows_pad = V.shape[0]
+    rows = rows_pad if rows is None else int(rows)
+    rs = [np.ascontiguousarray(r, dtype=np.float64) for r in rowscales]
+    if len(rs) > 2 or any(r.shape != (rows,) for r in rs):
+        raise ValueError("at most two row scales, of `rows` factors each")
+    if peers is not None:
+        peers = np.ascontiguousarray(peers, dtype=np.float64)
+        if peers.ndim != 2 or peers.shape[1] != 64:
+            raise ValueError("peers is (G - 1) x 64")
+    nsc = C.c_int(0)
+    check(lib().fpca_debug_i8_nsc_pad(int(S), int(b), C.byref(nsc)))
+    nsc, nops = nsc.value, max(1, len(rs))
+    res, structs, keep = [], [], []
+    for o in range(nops):
+        a = dict(colmax=np.empty(64), maxbits_own=np.empty((8, 64), dtype=np.uint64), maxbits=np.empty((8, 64), dtype=np.uint64),
+                 Q=np.empty((nsc, rows_pad), dtype=np.int8), colw=np.empty(nsc))
+        if colsum[o]:
+            a["colsum"] = np.empty((8, 640), dtype=np.int64)
+        if copy[o] is not None:
+            a["copy%d" % copy[o]] = np.empty((rows_pad, b), dtype=np.float32 if copy[o] == 32 else np.float64)
+        if route == 1:
+            a["Qrm"] = np.empty((rows_pad, S * b), dtype=np.int8)
+            for w in dequant:
+                a["dq%d" % w] = np.empty((rows_pad, b), dtype=np.float32 if w == 32 else np.float64)
+        st = _lib.SlicesOut()
+        for name, arr in a.items():
+            setattr(st, name, arr.ctypes.data)
+        structs.append(st)
+        res.append(a)
+    got = C.c_int(0)
+    check(lib().fpca_debug_i8_slices(int(route), int(b), int(S), rows, rows_pad, int(rows_valid), _p(V), _p(rs[0]) if rs else None,
+                                     _p(rs[1]) if len(rs) > 1 else None, _p(peers), 0 if peers is None else peers.shape[0], C.byref(structs[0]),
+                                     C.byref(structs[1]) if nops > 1 else None, C.byref(got)))
+    for a in res:
+        a["nsc_pad"] = got.value
+        if "colsum" in a:
+            a["colsum_shards"] = a["colsum"]
+            a["colsum"] = a["colsum_shards"].sum(axis=0)
+    return res
+
+
 def flashpca(X, ndim=10, stand="binom2", divisor="p", maxiter=500, tol=1e-6, do_loadings=False, return_scale=True,
              device=0, verbose=False, accum="auto", keep=None, snps=None, maf=0.0, geno=1.0, ld=None, unrelated=None,
              mind=1.0, hwe=0.0, **solver_kw):

@@ -1,6 +1,9 @@
 // bench_hooks.hip -- include/fpca_debug.h: measurement hooks (HIP-event timing of the operator's stages) and hardware probes.
 // Not part of the drop-in boundary.
 #include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
 #include <vector>
 
 #include "../../include/fpca_debug.h"
@@ -444,6 +447,157 @@ int fpca_debug_gather(int b, int use_f32, const uint32_t *ptr, const uint32_t *i
          kern::sparse_rows_sum(d_ptr, d_idx, static_cast<const double *>(d_V), d_rs, b, nrec, rows_out, d_out, nullptr, d_init, short_lists != 0, avg_len);
       HIP_CHECK(hipDeviceSynchronize());
       HIP_CHECK(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));
+   });
+}
+
+// The slicing kernels of the exact-integer arithmetic on caller data, through the launchers the operator calls (kern::i8_colmax ...
+// i8_dequant_rows) and in its order: route 0 = xt_i8 / x_i8's own slicing, route 1 = exchange_slices + the unpacking of apply_sharded.
+// Everything a kernel should write is poisoned first; every argument is checked before the device is touched.
+int fpca_debug_i8_nsc_pad(int S, int b, int *nsc_pad)
+{
+   return guarded([&] {
+      if (b != 16 && b != 32 && b != 48 && b != 64) throw Error(FPCA_EINVAL, "fpca_debug_i8_nsc_pad: b must be 16, 32, 48 or 64");
+      if (S < 2 || S > 8) throw Error(FPCA_EINVAL, "fpca_debug_i8_nsc_pad: S must be 2 .. 8");
+      if (!nsc_pad) throw Error(FPCA_EINVAL, "fpca_debug_i8_nsc_pad: nsc_pad is NULL");
+      *nsc_pad = kern::gemm_i8_nsc_pad(S, b);
+   });
+}
+
+int fpca_debug_i8_slices(int route, int b, int S, uint64_t rows, uint64_t rows_pad, uint64_t rows_valid, const double *V, const double *rowscale0,
+                         const double *rowscale1, const double *peers, int n_peers, fpca_debug_slices_out *out0, fpca_debug_slices_out *out1,
+                         int *nsc_pad)
+{
+   return guarded([&] {
+      static const char *FN = "fpca_debug_i8_slices";
+      auto bad = [&](const char *what) { throw Error(FPCA_EINVAL, std::string(FN) + ": " + what); };
+      if (route != 0 && route != 1) bad("route must be 0 (the operator's slicing) or 1 (the exchange)");
+      if (b != 16 && b != 32 && b != 48 && b != 64) bad("b must be 16, 32, 48 or 64");
+      if (S < 2 || S > 8) bad("S must be 2 .. 8");
+      if (rows_pad < 16 || rows_pad % 16 || rows_pad > (1ull << 20)) bad("rows_pad must be a multiple of 16 from 16 to 2^20");
+      if (rows > rows_pad) bad("rows is larger than rows_pad");
+      if (rows_valid > rows_pad) bad("rows_valid is larger than rows_pad");
+      if (!V) bad("V is NULL");
+      if (!out0) bad("out0 is NULL");
+      if (rowscale1 && !rowscale0) bad("rowscale1 is given without rowscale0");
+      if ((rowscale1 != nullptr) != (out1 != nullptr)) bad("out1 goes with rowscale1: the second operand");
+      const int nops = rowscale1 ? 2 : 1;
+      if (route == 1 && nops == 2) bad("rowscale1: the exchange (route 1) has one operand");
+      if (route == 1 && S * b > 512) bad("S b is larger than 512 on the exchange (route 1)");
+      if (n_peers < 0 || n_peers > 63 || (n_peers > 0) != (peers != nullptr)) bad("n_peers must be 0 .. 63 and go with peers");
+      if (n_peers && nops == 2) bad("peers go with one operand");
+      fpca_debug_slices_out *outs[2] = {out0, out1};
+      for (int o = 0; o < nops; o++) {
+         const fpca_debug_slices_out &w = *outs[o];
+         if (w.copy32 && w.copy64) bad("copy32 and copy64 of one operand: the operator asks for one of them");
+         if ((w.copy32 || w.dq32) && S > 4) bad("copy32 / dq32 need S <= 4: fp32 rows hold the 30 bits of four slices and no more");
+         if (route == 0 && (w.Qrm || w.dq32 || w.dq64)) bad("Qrm, dq32 and dq64 belong to the exchange (route 1)");
+      }
+      const double *rs[2] = {rowscale0, rowscale1};
+      for (uint64_t t = 0; t < rows * (uint64_t)b; t++)
+         if (!std::isfinite(V[t])) bad("V holds a non-finite entry");
+      for (int o = 0; o < nops; o++)
+         for (uint64_t r = 0; rs[o] && r < rows; r++)
+            if (!std::isfinite(rs[o][r])) bad(o ? "rowscale1 holds a non-finite entry" : "rowscale0 holds a non-finite entry");
+      for (int t = 0; t < n_peers * 64; t++)
+         if (!std::isfinite(peers[t]) || peers[t] < 0.0) bad("peers holds an entry that is not a finite maximum of magnitudes");
+
+      const int nsc = kern::gemm_i8_nsc_pad(S, b), SB = S * b, G = 1 + n_peers;
+      if (nsc_pad) *nsc_pad = nsc;
+      const size_t n_v = (size_t)rows_pad * b, n_max = 64 * kern::I8_SHARDS, n_cs = (size_t)kern::I8_CS_STRIDE * kern::I8_SHARDS;
+      auto nan_fill = [](void *p, size_t bytes) { HIP_CHECK(hipMemset(p, 0xFF, bytes)); }; // all bits set: a NaN in either width
+
+      DevMem<double> dV(n_v, FN, "the operand block"), dAll((size_t)G * 64, FN, "the gathered maxima");
+      HIP_CHECK(hipMemset(dV.p, 0, n_v * sizeof(double))); // rows >= rows are zero, as in the operator's blocks
+      if (rows) HIP_CHECK(hipMemcpy(dV.p, V, (size_t)rows * b * sizeof(double), hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemset(dAll.p, 0xFF, (size_t)G * 64 * sizeof(double)));
+      if (n_peers) HIP_CHECK(hipMemcpy(dAll.p + 64, peers, (size_t)n_peers * 64 * sizeof(double), hipMemcpyHostToDevice));
+      DevMem<int8_t> dQrm(route == 1 ? (size_t)rows_pad * SB : 0, FN, "the row-major slices");
+      if (dQrm.p) HIP_CHECK(hipMemset(dQrm.p, 0x55, (size_t)rows_pad * SB));
+
+      struct Dev { // one operand's buffers
+         DevMem<double> rs, colw, c64, q64;
+         DevMem<unsigned long long> maxbits;
+         DevMem<int8_t> Q;
+         DevMem<long long> colsum;
+         DevMem<float> c32, q32;
+      } dev[2];
+      kern::SliceOp ops[2];
+      std::vector<unsigned long long> own_bits[2];
+      for (int o = 0; o < nops; o++) {
+         Dev &d = dev[o];
+         const fpca_debug_slices_out &w = *outs[o];
+         if (rs[o]) {
+            d.rs = DevMem<double>(rows_pad, FN, "a row scale");
+            HIP_CHECK(hipMemset(d.rs.p, 0, rows_pad * sizeof(double)));
+            if (rows) HIP_CHECK(hipMemcpy(d.rs.p, rs[o], rows * sizeof(double), hipMemcpyHostToDevice));
+         }
+         d.maxbits = DevMem<unsigned long long>(n_max, FN, "the column maxima");
+         d.Q = DevMem<int8_t>((size_t)nsc * rows_pad, FN, "the slices");
+         d.colw = DevMem<double>(nsc, FN, "the weights");
+         d.colsum = DevMem<long long>(n_cs, FN, "the column sums");
+         HIP_CHECK(hipMemset(d.maxbits.p, 0, n_max * sizeof(unsigned long long))); // (zeroed once per apply, as the operator does)
+         HIP_CHECK(hipMemset(d.colsum.p, 0, n_cs * sizeof(long long)));
+         HIP_CHECK(hipMemset(d.Q.p, 0x55, (size_t)nsc * rows_pad));
+         nan_fill(d.colw.p, nsc * sizeof(double));
+         if (w.copy32) d.c32 = DevMem<float>(n_v, FN, "the fp32 copy");
+         if (w.copy64) d.c64 = DevMem<double>(n_v, FN, "the fp64 copy");
+         if (w.dq32) d.q32 = DevMem<float>(n_v, FN, "the fp32 rows");
+         if (w.dq64) d.q64 = DevMem<double>(n_v, FN, "the fp64 rows");
+         if (d.c32.p) nan_fill(d.c32.p, n_v * sizeof(float));
+         if (d.c64.p) nan_fill(d.c64.p, n_v * sizeof(double));
+         if (d.q32.p) nan_fill(d.q32.p, n_v * sizeof(float));
+         if (d.q64.p) nan_fill(d.q64.p, n_v * sizeof(double));
+         // route 1 hands the copies to i8_unpack_slices itself, as apply_sharded's callers do: the SliceOp carries none
+         ops[o] = kern::SliceOp{d.rs.p, d.maxbits.p, d.Q.p, d.colw.p, w.colsum ? d.colsum.p : nullptr, route == 0 ? d.c64.p : nullptr,
+                                route == 0 ? d.c32.p : nullptr};
+      }
+
+      hipStream_t s = nullptr;
+      kern::i8_colmax(dV.p, route == 0 ? rows : rows_pad, b, nops, ops, s);
+      HIP_CHECK(hipDeviceSynchronize());
+      for (int o = 0; o < nops; o++) {
+         own_bits[o].resize(n_max);
+         HIP_CHECK(hipMemcpy(own_bits[o].data(), ops[o].maxbits, n_max * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+      }
+      if (nops == 1) kern::i8_maxbits_fold(ops[0].maxbits, dAll.p, s); // the hook's own answer is row 0 of the gathered maxima
+      if (route == 1 || n_peers) kern::i8_maxbits_set(dAll.p, G, ops[0].maxbits, s);
+      if (route == 0)
+         kern::i8_slice(dV.p, rows_pad, rows, b, S, nops, ops, s);
+      else {
+         kern::i8_slice_rows(dV.p, rows_pad, b, S, ops[0], dQrm.p, s);
+         kern::i8_unpack_slices(dQrm.p, rows_pad, b, S, ops[0], s, rows_valid, dev[0].c32.p, dev[0].c64.p);
+         if (dev[0].q32.p) kern::i8_dequant_rows(dQrm.p, rows_pad, b, S, ops[0], dev[0].q32.p, nullptr, s);
+         if (dev[0].q64.p) kern::i8_dequant_rows(dQrm.p, rows_pad, b, S, ops[0], nullptr, dev[0].q64.p, s);
+      }
+      HIP_CHECK(hipDeviceSynchronize());
+
+      for (int o = 0; o < nops; o++) {
+         const fpca_debug_slices_out &w = *outs[o];
+         const Dev &d = dev[o];
+         auto down = [&](void *h, const void *p, size_t bytes) {
+            if (h) HIP_CHECK(hipMemcpy(h, p, bytes, hipMemcpyDeviceToHost));
+         };
+         if (w.colmax) {
+            if (nops == 1)
+               down(w.colmax, dAll.p, 64 * sizeof(double));
+            else // (two operands: no launch of the fold; the same maximum over the shards, of the words downloaded above)
+               for (int c = 0; c < 64; c++) {
+                  unsigned long long m = 0;
+                  for (int k = 0; k < kern::I8_SHARDS; k++) m = std::max(m, own_bits[o][k * 64 + c]);
+                  std::memcpy(&w.colmax[c], &m, sizeof(double));
+               }
+         }
+         if (w.maxbits_own) std::memcpy(w.maxbits_own, own_bits[o].data(), n_max * sizeof(unsigned long long));
+         down(w.maxbits, d.maxbits.p, n_max * sizeof(unsigned long long));
+         down(w.Q, d.Q.p, (size_t)nsc * rows_pad);
+         down(w.Qrm, dQrm.p, (size_t)rows_pad * SB);
+         down(w.colw, d.colw.p, nsc * sizeof(double));
+         down(w.colsum, d.colsum.p, n_cs * sizeof(long long));
+         down(w.copy32, d.c32.p, n_v * sizeof(float));
+         down(w.copy64, d.c64.p, n_v * sizeof(double));
+         down(w.dq32, d.q32.p, n_v * sizeof(float));
+         down(w.dq64, d.q64.p, n_v * sizeof(double));
+      }
    });
 }
 

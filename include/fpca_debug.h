@@ -108,6 +108,47 @@ int fpca_debug_gather(int b, int use_f32, const uint32_t *ptr, const uint32_t *i
                       const double *rowscale, const double *colw, const double *init, uint64_t nrec, uint64_t rows_out, int short_lists,
                       double avg_len, double *out, int *variant);
 
+/* diagnostic (tests/test_gpu_i8_slices.py): the kernels that cut an fp64 operand into the int8 digit planes of the exact-integer
+ * arithmetic (csrc/kernels_i8.hip, top), on caller data, host pointers, no context -- through the host launchers the operator calls, in
+ * the operator's order.  V: rows_pad x b fp64 row-major (b = 16, 32, 48 or 64; rows_pad a multiple of 16 up to 2^20); rows >= `rows`
+ * are not read: the device block holds zeros there, as the operator's blocks do.  S = 2 .. 8 slices.  rowscale0 / rowscale1 (may be
+ * NULL; `rows` factors each): none = one operand V; rowscale0 alone = one operand V diag(rowscale0); both = the two operands of X T from
+ * one pass (route 0 only), the second answered in out1.  peers (may be NULL): n_peers x 64 column maxima standing for the other ranks'
+ * answers to the small all-gather; one operand only.
+ *   route 0, the operator's own slicing:  maxbits zeroed; i8_colmax over `rows`; with peers i8_maxbits_fold + i8_maxbits_set over
+ *            [own; peers]; i8_slice.
+ *   route 1, the row-sharded exchange:    maxbits zeroed; i8_colmax over rows_pad; i8_maxbits_fold; i8_maxbits_set over [own; peers];
+ *            i8_slice_rows over rows_pad rows -> Qrm; i8_unpack_slices(Qrm, rows_valid, the copies); i8_dequant_rows(Qrm) once per
+ *            requested output.  S b <= 512.
+ * Before the launches Q (all nsc_pad rows) and Qrm are filled with the byte 0x55, colw (all nsc_pad entries) and every requested copy with
+ * NaNs (all bits set), and colsum with zeros: what a kernel does not write, or writes where it should not, shows.
+ * Every member of fpca_debug_slices_out is a host buffer or NULL (not wanted); colsum, copy32, copy64, dq32 and dq64 are also the switch:
+ * the kernels are asked for what is not NULL.  At most one of copy32 / copy64 per operand, and fp32 rows with S <= 4 only, as the operator
+ * asks.  *nsc_pad (may be NULL): the padded number of slice-columns, gemm_i8_nsc_pad(S, b); fpca_debug_i8_nsc_pad returns it alone, for
+ * sizing Q and colw, and touches no device.
+ * FPCA_EINVAL, with a message that names the argument, before anything touches the device: route not 0 / 1; b or S outside their sets;
+ * rows_pad not a multiple of 16 in 16 .. 2^20; rows or rows_valid > rows_pad; V or out0 NULL; rowscale1 without rowscale0, or without
+ * out1, or out1 without it; rowscale1 or S b > 512 on route 1; n_peers outside 0 .. 63 or not matching peers; peers with two operands;
+ * both copies, or fp32 rows with S > 4; Qrm / dq32 / dq64 on route 0; a non-finite entry in V (rows < `rows`), a row scale or peers, or
+ * a negative one in peers. */
+typedef struct fpca_debug_slices_out {
+   double *colmax;        /* [64] the operand's own column maxima, shards folded (route 0 with one operand and route 1: by i8_maxbits_fold) */
+   uint64_t *maxbits_own; /* [8][64] the sharded maxima as i8_colmax left them, bit patterns of doubles */
+   uint64_t *maxbits;     /* [8][64] the same as the slicing kernels read them: after i8_maxbits_set where it ran */
+   int8_t *Q;             /* [nsc_pad][rows_pad] */
+   int8_t *Qrm;           /* [rows_pad][S b], route 1 */
+   double *colw;          /* [nsc_pad] */
+   int64_t *colsum;       /* [8][640] per shard: the sum over the shards is the column sum */
+   float *copy32;         /* [rows_pad][b] from i8_slice (route 0) or i8_unpack_slices (route 1: rows < rows_valid) */
+   double *copy64;        /* the same in fp64 */
+   float *dq32;           /* [rows_pad][b] from i8_dequant_rows, route 1 */
+   double *dq64;
+} fpca_debug_slices_out;
+int fpca_debug_i8_nsc_pad(int S, int b, int *nsc_pad);
+int fpca_debug_i8_slices(int route, int b, int S, uint64_t rows, uint64_t rows_pad, uint64_t rows_valid, const double *V, const double *rowscale0,
+                         const double *rowscale1, const double *peers, int n_peers, fpca_debug_slices_out *out0, fpca_debug_slices_out *out1,
+                         int *nsc_pad);
+
 /* diagnostic (tests): the F tail of fpca_ucca, from the host build of the same source the finishing kernel runs (no device
  * involved): F = r2 / (1 - r2) (n - k - 1) / k and P = upper tail of F(k, n - k - 1) at F = I_{1 - r2}((n - k - 1) / 2, k / 2).
  * FPCA_EINVAL unless k >= 1 and n >= k + 2. */

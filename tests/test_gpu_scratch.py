@@ -200,6 +200,20 @@ def test_debug_gather(env):
     _run(env, "fpca_debug_gather", lambda: (debug_gather(ptr, idx, V, b, rows_out=80, rowscale=rs, init=np.ones((80, b)))[0],))
 
 
+def test_debug_i8_slices(env):
+    from flashpca_amd.api import debug_i8_slices
+
+    rng = np.random.default_rng(6)
+    V, peers = rng.standard_normal((48, 16)), rng.uniform(0.0, 9.0, (2, 64))
+
+    def both_routes():
+        a, = debug_i8_slices(V, 16, 4, rows=45, route=0, rowscales=[np.full(45, 2.0)], peers=peers, copy=(32, None))
+        b, = debug_i8_slices(V, 16, 4, rows=45, route=1, peers=peers, rows_valid=40, copy=(32, None), dequant=(32, 64))
+        return a["Q"], a["colw"], a["colsum"], a["copy32"], b["Q"], b["Qrm"], b["colw"], b["colsum"], b["copy32"], b["dq32"], b["dq64"]
+
+    _run(env, "fpca_debug_i8_slices", both_routes)
+
+
 def test_bench_hooks(env):
     ctx, L = env["ctx"], env["L"]
 
