@@ -126,86 +126,144 @@ void fill_missing(const uint8_t *packed, size_t pitch, uint64_t ncols, uint64_t 
    launch_check();
 }
 
+// two adjacent columns of a row, fetched by one load (16 bytes of an fp64 row, 8 of an fp32 one)
+template <class VT>
+struct ColPair;
+template <>
+struct ColPair<double> {
+   typedef double2 type;
+};
+template <>
+struct ColPair<float> {
+   typedef float2 type;
+};
+
 // out[r][c] = sum over s in list(r) of V[s][c] * (rowscale ? rowscale[s] : 1)   (fp64, list order = ascending s);
-// rows r >= nrec are zeroed.  One wave per output row; EPW = 64 / b list entries per step, 4 steps in flight.
+// rows r >= nrec are zeroed.  One wave per output row.  A lane holds two adjacent columns, B / 2 lanes a row: 2 EPW = 128 / b list
+// entries per step, 2 steps in flight.  The sums are those of one column per lane with EPW entries per step and 4 steps in flight,
+// bit for bit: entry n of a list goes to partial sum n mod 4 EPW, which is accumulator (n / 2 EPW) mod 2 of lane group n mod 2 EPW
+// here and was accumulator (n / EPW) mod 4 of lane group n mod EPW there; the partial sums of a column are then added in the order
+// (a0 + a1) + (a2 + a3) per old lane group -- a0, a2 from lane group g, a1, a3 from lane group g + EPW, 32 lanes up -- and across
+// the old lane groups by the same tree.
 template <int B, class VT>
 __global__ __launch_bounds__(256) void k_sparse_rows_sum(const uint32_t *__restrict__ ptr, const uint32_t *__restrict__ idx,
                                                           const VT *__restrict__ V, const double *__restrict__ rowscale, uint64_t nrec,
                                                           uint64_t rows_out, double *__restrict__ out, const double *__restrict__ init,
                                                           const double *__restrict__ colw)
 {
-   constexpr int EPW = 64 / B;
-   const int lane = threadIdx.x & 63, c = lane % B, e0 = lane / B;
+   typedef typename ColPair<VT>::type V2;
+   constexpr int EPW = 64 / B, LPR = B / 2, G2 = 2 * EPW;
+   const int lane = threadIdx.x & 63, c2 = lane % LPR, e0 = lane / LPR;
+   const V2 *__restrict__ V2p = reinterpret_cast<const V2 *>(V);
    for (uint64_t r = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows_out; r += (uint64_t)gridDim.x * 4) {
-      double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+      double a0x = 0.0, a0y = 0.0, a1x = 0.0, a1y = 0.0;
       if (r < nrec) {
          const uint32_t p0 = ptr[r], p1 = ptr[r + 1];
-         for (uint32_t t = p0 + e0; t < p1; t += 4 * EPW) {
-            const uint32_t t1 = t + EPW, t2 = t + 2 * EPW, t3 = t + 3 * EPW;
-            const uint32_t s0 = idx[t], s1 = t1 < p1 ? idx[t1] : 0, s2 = t2 < p1 ? idx[t2] : 0, s3 = t3 < p1 ? idx[t3] : 0;
-            double v0 = V[(uint64_t)s0 * B + c], v1 = t1 < p1 ? V[(uint64_t)s1 * B + c] : 0.0, v2 = t2 < p1 ? V[(uint64_t)s2 * B + c] : 0.0,
-                   v3 = t3 < p1 ? V[(uint64_t)s3 * B + c] : 0.0;
-            if (rowscale) {
-               v0 *= rowscale[s0];
-               v1 *= t1 < p1 ? rowscale[s1] : 0.0;
-               v2 *= t2 < p1 ? rowscale[s2] : 0.0;
-               v3 *= t3 < p1 ? rowscale[s3] : 0.0;
+         for (uint32_t t = p0 + e0; t < p1; t += 2 * G2) {
+            const uint32_t t1 = t + G2;
+            const uint32_t s0 = idx[t], s1 = t1 < p1 ? idx[t1] : 0;
+            const V2 w0 = V2p[(uint64_t)s0 * LPR + c2];
+            double v0x = w0.x, v0y = w0.y, v1x = 0.0, v1y = 0.0;
+            if (t1 < p1) {
+               const V2 w1 = V2p[(uint64_t)s1 * LPR + c2];
+               v1x = w1.x;
+               v1y = w1.y;
             }
-            a0 += v0;
-            a1 += v1;
-            a2 += v2;
-            a3 += v3;
+            if (rowscale) {
+               const double f0 = rowscale[s0], f1 = t1 < p1 ? rowscale[s1] : 0.0;
+               v0x *= f0;
+               v0y *= f0;
+               v1x *= f1;
+               v1y *= f1;
+            }
+            a0x += v0x;
+            a0y += v0y;
+            a1x += v1x;
+            a1y += v1y;
          }
       }
-      double a = (a0 + a1) + (a2 + a3);
+      a0x += __shfl_down(a0x, 32);
+      a0y += __shfl_down(a0y, 32);
+      a1x += __shfl_down(a1x, 32);
+      a1y += __shfl_down(a1y, 32);
+      double ax = a0x + a1x, ay = a0y + a1y;
 #pragma unroll
-      for (int o = 32; o >= B; o >>= 1) a += __shfl_down(a, o);
-      if (lane < B) {
-         if (colw) a *= colw[c] * 32.0; // fp32 rows were stored as x 2^(1 - e_c); colw[c] = 2^(e_c - 6) (top slice's weight)
-         out[r * B + c] = init ? init[r * B + c] + a : a;
+      for (int o = 16; o >= LPR; o >>= 1) {
+         ax += __shfl_down(ax, o);
+         ay += __shfl_down(ay, o);
+      }
+      if (lane < LPR) {
+         const int c = 2 * c2;
+         if (colw) { // fp32 rows were stored as x 2^(1 - e_c); colw[c] = 2^(e_c - 6) (top slice's weight)
+            ax *= colw[c] * 32.0;
+            ay *= colw[c + 1] * 32.0;
+         }
+         out[r * B + c] = init ? init[r * B + c] + ax : ax;
+         out[r * B + c + 1] = init ? init[r * B + c + 1] + ay : ay;
       }
    }
 }
 
 // The same sum with the index list read in coalesced batches of 64 (one entry per lane, broadcast by shuffles) instead of
 // one dependent 4-byte load per gathered row: the loop above is a chain idx -> row of V, both at Infinity-Cache latency,
-// with four rows in flight per wave; here the rows of a batch are independent of any further index load and eight of them
+// with two row pieces in flight per lane; here the rows of a batch are independent of any further index load and four pieces
 // are in flight (per lane slot).  The per-row factors of a batch are gathered once, one per lane, the same way.
+// (Two columns per lane as above: partial sum n mod 8 EPW of a column is accumulator (n / 2 EPW) mod 4 of lane group n mod 2 EPW,
+// was accumulator (n / EPW) mod 8 of lane group n mod EPW, and the additions keep their order.)
 template <int B, class VT>
 __global__ __launch_bounds__(256) void k_sparse_rows_sum_batched(const uint32_t *__restrict__ ptr, const uint32_t *__restrict__ idx,
                                                                   const VT *__restrict__ V, const double *__restrict__ rowscale,
                                                                   uint64_t nrec, uint64_t rows_out, double *__restrict__ out, const double *__restrict__ init,
                                                                   const double *__restrict__ colw)
 {
-   constexpr int EPW = 64 / B, U = 8;
-   const int lane = threadIdx.x & 63, c = lane % B, e0 = lane / B;
+   typedef typename ColPair<VT>::type V2;
+   constexpr int EPW = 64 / B, LPR = B / 2, G2 = 2 * EPW, U = 4;
+   const int lane = threadIdx.x & 63, c2 = lane % LPR, e0 = lane / LPR;
+   const V2 *__restrict__ V2p = reinterpret_cast<const V2 *>(V);
    for (uint64_t r = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows_out; r += (uint64_t)gridDim.x * 4) {
-      double acc[U];
+      double accx[U], accy[U];
 #pragma unroll
-      for (int u = 0; u < U; u++) acc[u] = 0.0;
+      for (int u = 0; u < U; u++) accx[u] = accy[u] = 0.0;
       if (r < nrec) {
          const uint32_t p0 = ptr[r], p1 = ptr[r + 1];
          for (uint32_t t0 = p0; t0 < p1; t0 += 64) {
             const int cnt = (int)(p1 - t0 < 64u ? p1 - t0 : 64u);
             const uint32_t mine = lane < cnt ? idx[t0 + lane] : 0u;
             const double myscale = (rowscale && lane < cnt) ? rowscale[mine] : 1.0;
-            for (int u0 = 0; u0 < cnt; u0 += EPW * U) {
+            for (int u0 = 0; u0 < cnt; u0 += G2 * U) {
 #pragma unroll
                for (int u = 0; u < U; u++) {
-                  const int e = u0 + u * EPW + e0;
+                  const int e = u0 + u * G2 + e0;
                   const uint32_t srow = (uint32_t)__shfl((int)mine, e & 63);
                   const double sc = __shfl(myscale, e & 63);
-                  if (e < cnt) acc[u] += V[(uint64_t)srow * B + c] * sc;
+                  if (e < cnt) {
+                     const V2 w = V2p[(uint64_t)srow * LPR + c2];
+                     accx[u] += w.x * sc;
+                     accy[u] += w.y * sc;
+                  }
                }
             }
          }
       }
-      double a = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
 #pragma unroll
-      for (int o = 32; o >= B; o >>= 1) a += __shfl_down(a, o);
-      if (lane < B) {
-         if (colw) a *= colw[c] * 32.0; // fp32 rows were stored as x 2^(1 - e_c); colw[c] = 2^(e_c - 6) (top slice's weight)
-         out[r * B + c] = init ? init[r * B + c] + a : a;
+      for (int u = 0; u < U; u++) {
+         accx[u] += __shfl_down(accx[u], 32);
+         accy[u] += __shfl_down(accy[u], 32);
+      }
+      double ax = (accx[0] + accx[1]) + (accx[2] + accx[3]), ay = (accy[0] + accy[1]) + (accy[2] + accy[3]);
+#pragma unroll
+      for (int o = 16; o >= LPR; o >>= 1) {
+         ax += __shfl_down(ax, o);
+         ay += __shfl_down(ay, o);
+      }
+      if (lane < LPR) {
+         const int c = 2 * c2;
+         if (colw) { // fp32 rows were stored as x 2^(1 - e_c); colw[c] = 2^(e_c - 6) (top slice's weight)
+            ax *= colw[c] * 32.0;
+            ay *= colw[c + 1] * 32.0;
+         }
+         out[r * B + c] = init ? init[r * B + c] + ax : ax;
+         out[r * B + c + 1] = init ? init[r * B + c + 1] + ay : ay;
       }
    }
 }
