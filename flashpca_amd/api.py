@@ -693,6 +693,16 @@ def debug_i8_slices(V, b, S, rows=None, route=0, rowscales=(), peers=None, rows_
     return res
 
 
+def debug_i8_instances():
+    """fpca_debug_i8_instances: every int8 GEMM kernel instance as a tuple (two operands, mode, nt, half tile, tile rows, band-tiled), in the
+    order of the table; host only."""
+    n = C.c_int(0)
+    check(lib().fpca_debug_i8_instances(None, 0, C.byref(n)))
+    keys = np.zeros((n.value, 6), dtype=np.int32)
+    check(lib().fpca_debug_i8_instances(_p(keys), n.value, C.byref(n)))
+    return [(bool(k[0]), int(k[1]), int(k[2]), bool(k[3]), int(k[4]), bool(k[5])) for k in keys[:n.value]]
+
+
 def flashpca(X, ndim=10, stand="binom2", divisor="p", maxiter=500, tol=1e-6, do_loadings=False, return_scale=True,
              device=0, verbose=False, accum="auto", keep=None, snps=None, maf=0.0, geno=1.0, ld=None, unrelated=None,
              mind=1.0, hwe=0.0, **solver_kw):

@@ -463,6 +463,16 @@ int fpca_debug_i8_nsc_pad(int S, int b, int *nsc_pad)
    });
 }
 
+int fpca_debug_i8_instances(int32_t *keys, int cap, int *count)
+{
+   return guarded([&] {
+      if (!count) throw Error(FPCA_EINVAL, "fpca_debug_i8_instances: count is NULL");
+      if (cap < 0 || (cap > 0 && !keys)) throw Error(FPCA_EINVAL, "fpca_debug_i8_instances: keys is NULL or cap negative");
+      static_assert(sizeof(int32_t) == sizeof(int), "the keys travel as int");
+      *count = kern::gemm_i8_instances(reinterpret_cast<int(*)[6]>(keys), cap);
+   });
+}
+
 int fpca_debug_i8_slices(int route, int b, int S, uint64_t rows, uint64_t rows_pad, uint64_t rows_valid, const double *V, const double *rowscale0,
                          const double *rowscale1, const double *peers, int n_peers, fpca_debug_slices_out *out0, fpca_debug_slices_out *out1,
                          int *nsc_pad)

@@ -153,6 +153,8 @@ __host__ __device__ inline size_t packed_piece_offset(uint64_t r, uint64_t q, si
 }
 int gemm_i8_nsc_pad(int S, int b); // rows of a Q operand: S*b rounded up to the 256-column workgroup tile
 size_t gemm_i8_workspace_doubles(uint64_t rows_pad, uint64_t k_pad, int S, int b, bool two);
+// every k_gemm_i8 instance there is as (two operands, mode, nt, half tile, tile rows, band-tiled): writes min(count, cap), returns the count
+int gemm_i8_instances(int (*out)[6], int cap);
 // out[rows_pad][b] = recombined ( (G.M) Qg' , M Qm' ); mean/sd non-null: K2 flavour (per-row standardisation)
 void gemm_i8(const uint8_t *packed, size_t pitch, const int8_t *Qg, const int8_t *Qm, const double *wg, const double *wm,
              const long long *colsum_m, const double *mean, const double *sd, double *out, double *ws, uint64_t rows_pad, uint64_t k_pad,

@@ -1152,6 +1152,20 @@ constexpr bool i8_find(I8List<C...>, const I8Key &k, F &&f)
 {
    return ((k.two == C::TWO && k.mode == C::MODE && k.nt == C::NT && k.half == C::HALF && k.rows == C::ROWS && k.tiled == C::TILED && f(C{})) || ...);
 }
+// the key of every member of the list, in the list's order (fpca_debug_i8_instances: what a census of the launched instances is held to)
+template <class... C>
+static int i8_keys(I8List<C...>, int (*out)[6], int cap)
+{
+   const I8Key keys[] = {I8Key{C::TWO, C::MODE, C::NT, C::HALF, C::ROWS, C::TILED}...};
+   const int n = (int)sizeof...(C);
+   for (int i = 0; i < n && i < cap; i++) {
+      const int k[6] = {keys[i].two, keys[i].mode, keys[i].nt, keys[i].half, keys[i].rows, keys[i].tiled};
+      std::copy(k, k + 6, out[i]);
+   }
+   return n;
+}
+int gemm_i8_instances(int (*out)[6], int cap) { return i8_keys(I8Instances{}, out, cap); }
+
 constexpr bool i8_exists(bool two, int mode, int nt, bool half, int rows, bool tiled)
 {
    return i8_find(I8Instances{}, I8Key{two, mode, nt, half, rows, tiled}, [](auto) { return true; });

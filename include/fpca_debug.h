@@ -148,6 +148,12 @@ int fpca_debug_i8_nsc_pad(int S, int b, int *nsc_pad);
 int fpca_debug_i8_slices(int route, int b, int S, uint64_t rows, uint64_t rows_pad, uint64_t rows_valid, const double *V, const double *rowscale0,
                          const double *rowscale1, const double *peers, int n_peers, fpca_debug_slices_out *out0, fpca_debug_slices_out *out1,
                          int *nsc_pad);
+/* diagnostic (tests/test_gpu_i8_planes.py): the table of int8 GEMM kernel instances (csrc/kernels_i8.hip, I8Instances), host only, no
+ * device involved.  keys (may be NULL when cap is 0): cap rows of six int32 -- two operands (0 / 1), mode (0 both matrices, 1 the same
+ * skipping empty blocks of E, 2 G.M alone), nt (column tiles per workgroup), half tile (0 / 1), tile rows (128 / 256 / 512), band-tiled
+ * `packed` (0 / 1) -- in the table's order; min(*count, cap) rows are written.  *count: the number of instances.  A test that launches
+ * the GEMM under FPCA_I8_VERBOSE can rebuild the same six numbers from the plan and launch lines and hold its cases to the whole table. */
+int fpca_debug_i8_instances(int32_t *keys, int cap, int *count);
 
 /* diagnostic (tests): the F tail of fpca_ucca, from the host build of the same source the finishing kernel runs (no device
  * involved): F = r2 / (1 - r2) (n - k - 1) / k and P = upper tail of F(k, n - k - 1) at F = I_{1 - r2}((n - k - 1) / 2, k / 2).
