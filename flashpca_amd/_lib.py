@@ -181,6 +181,8 @@ SIGNATURES = {
     "fpca_debug_i8_slices": (_I, [_I, _I, _I, _U64, _U64, _U64, _P, _P, _P, _P, _I, C.POINTER(SlicesOut), C.POINTER(SlicesOut), C.POINTER(_I)]),
     "fpca_debug_i8_instances": (_I, [_P, _I, C.POINTER(_I)]),
     "fpca_debug_f_sf":(_I, [_D, _U64, _I, C.POINTER(_D), C.POINTER(_D)]),
+    "fpca_debug_f_sf_dev": (_I, [_P, _U64, _U64, _I, _P, _P]),
+    "fpca_debug_scca_lds": (_I, [_I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "fpca_debug_fold_stats": (_I, [_P, _P, _I, _P, _I, _P]),
     "fpca_debug_snp_qc_rule": (_I, [_P, _P, _U64, _U64, _D, _D, _P, C.POINTER(_U64)]),
     "fpca_debug_snp_subset_bench": (_I, [_P, _P, _I, C.POINTER(_D), C.POINTER(_D)]),

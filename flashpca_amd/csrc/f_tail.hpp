@@ -1,15 +1,23 @@
 // f_tail.hpp -- the upper tail of the F distribution for UCCA (RandomPCA::ucca -> wilks, randompca.cpp:103-119, where Boost's
 // fisher_f supplies it), as ONE __host__ __device__ source: the finishing kernel of ucca.hip runs it per SNP, and the host build of
-// the same code is exported as fpca_debug_f_sf for the CPU suite.
+// the same code is exported as fpca_debug_f_sf for the CPU suite (fpca_debug_f_sf_dev runs the device build on a grid of r2).
 //
 // With r2 the squared multiple correlation of a SNP on k phenotypes and n samples, F = r2 / (1 - r2) (n - k - 1) / k and
 //   P = Pr[F(k, n - k - 1) > F] = I_{1 - r2}(a, b),   a = (n - k - 1) / 2,  b = k / 2,
-// the regularised incomplete beta function, evaluated from r2 itself (never through F or a rounded 1 - r2: the logarithms of
-// both arguments come from log(r2) and log1p(-r2)).  The method is the classical one: the prefactor x^a y^b / (a B(a, b)) in log
-// space, the continued fraction by the modified Lentz algorithm, and the symmetry I_x(a, b) = 1 - I_y(b, a) on the side of the
-// mean where the fraction would converge slowly.  The one refinement: with a in the hundreds of thousands, lgamma(a + b) -
-// lgamma(a) is taken from the difference of the Stirling series rather than as a difference of two numbers near 10^7, so the
-// prefactor keeps its relative accuracy (~1e-13) all the way down to the smallest normal P.  Below ~1e-300 P underflows to 0.
+// the regularised incomplete beta function, evaluated from r2 itself and never through F: the logarithms of both arguments come
+// from log(r2) and log1p(-r2).  The method is the classical one: the prefactor x^a y^b / (a B(a, b)) in log space, the continued
+// fraction by the modified Lentz algorithm, and the symmetry I_x(a, b) = 1 - I_y(b, a) on the side of the mean where the fraction
+// would converge slowly.  The one refinement: with a in the hundreds of thousands, lgamma(a + b) - lgamma(a) is taken from the
+// difference of the Stirling series rather than as a difference of two numbers near 10^7, so the PREFACTOR keeps its relative
+// accuracy (~1e-13) all the way down to the smallest normal P.  Below ~1e-300 P underflows to 0.
+//
+// What holds for P as a whole, against scipy's betaincc(k/2, (n-k-1)/2, r2) wherever that is >= 1e-290, k <= 256 (the table
+// tests/test_gpu_f_tail.py prints, the device build on the MI355X and the host build alike; the tests assert 1e-8):
+//     n <= 10: 1.9e-14     n = 957: 2.5e-13     n = 500,000: 3.1e-11     n = 1,000,000: 6.4e-11 (k = 1, r2 = 4.4e-6, P = 0.036)
+// The loss at large n is not the prefactor's.  It sits on the I_x(a, b) side of the switch (x = 1 - r2 < (a + 1) / (a + b + 2)), just
+// above it -- r2 of a few k / n, where most SNPs of a large scan lie: the FRACTION there receives the rounded 1.0 - r2, a relative
+// error of eps / r2 in y = r2, and carries it into P.  Making the first Lentz term cancellation-free repairs k = 2 alone; a fraction
+// re-derived in y would repair the rest and has not been done.
 #pragma once
 #include <cmath>
 #include <cstdint>

@@ -589,12 +589,23 @@ extern "C" int fpca_scca_prepare(fpca_ctx *ctx, const double *Y, int64_t ldy, in
       if (k < 1) throw Error(FPCA_EINVAL, "fpca_scca_prepare needs at least one phenotype (k >= 1)");
       if (k > SCCA_MAX_K)
          throw Error(FPCA_EINVAL, "fpca_scca_prepare: " + std::to_string(k) + " phenotypes; at most " + std::to_string(SCCA_MAX_K) +
-                                      " are supported (the k-sized step keeps two vectors of that length in the 64 KB of one workgroup's LDS)");
+                                      " are supported (the k-sized step keeps two vectors of that length in one workgroup's LDS: " +
+                                      std::to_string(SCCA_V_LDS_MAX) + " B at the maximum, of the 160 KB gfx950 gives a workgroup)");
       if (ldy < (int64_t)ctx->N) throw Error(FPCA_EINVAL, "fpca_scca_prepare: ldy is smaller than the number of samples");
       if (stand_y < FPCA_STANDARDISE_NONE || stand_y > FPCA_STANDARDISE_CENTER)
          throw Error(FPCA_EINVAL, "fpca_scca_prepare: unknown phenotype standardisation " + std::to_string(stand_y));
       if (ctx->N < 2) throw Error(FPCA_EINVAL, "fpca_scca_prepare needs at least two samples");
       scca_prepare(ctx, Y, ldy, k, stand_y, divisor);
+   });
+}
+
+extern "C" int fpca_debug_scca_lds(int device, int *max_k, int *need_at_max_k, int *per_workgroup)
+{
+   return guarded([&] {
+      if (!max_k || !need_at_max_k || !per_workgroup) throw Error(FPCA_EINVAL, "bad argument to fpca_debug_scca_lds (NULL pointer)");
+      *max_k = SCCA_MAX_K;
+      *need_at_max_k = SCCA_V_LDS_MAX;
+      HIP_CHECK(hipDeviceGetAttribute(per_workgroup, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
    });
 }
 

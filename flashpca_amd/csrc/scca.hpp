@@ -23,7 +23,11 @@ struct fpca_scca_state {
 
 namespace fpca {
 
-constexpr int SCCA_MAX_K = 3840; // k_scca_v keeps w and v (2 * k_pad doubles) in LDS
+// k_scca_v<1024> keeps w and v (2 * k_pad doubles, dynamic) beside its buf [1024] and red [16] (static, 8,320 B by the code object's
+// metadata) in LDS: 69,760 B at the maximum, of the 160 KB one workgroup may use on gfx950 (64 KB would stop at k = 3568)
+constexpr int SCCA_MAX_K = 3840;
+constexpr int SCCA_V_LDS_MAX = 8 * (1024 + 16) + 2 * 8 * SCCA_MAX_K;
+static_assert(SCCA_MAX_K % 16 == 0 && SCCA_V_LDS_MAX <= 160 * 1024, "k_scca_v at SCCA_MAX_K does not fit one workgroup's LDS");
 
 // one model as scca_fit_dev leaves it: U [ndim][P_g] and V [ndim][kp] in the state's workspace (valid until the next fit on that
 // state), everything of length ndim on the host

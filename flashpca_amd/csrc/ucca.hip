@@ -1,5 +1,5 @@
 // ucca.hip -- per-SNP association with k phenotypes (RandomPCA::ucca, randompca.cpp:530-625 + wilks, :103-119; plink.multivariate):
-// fpca_ucca and the host build of its F tail, fpca_debug_f_sf.
+// fpca_ucca and the two builds of its F tail on their own: fpca_debug_f_sf (host) and fpca_debug_f_sf_dev (device).
 //
 // The reference takes the SVD Y = U D V' of the standardised phenotypes and, SNP by SNP, r2_j = |sum (cov(x_j, Y) V sqrt(n-1) / d)^2|
 // / var(x_j).  Since V D^-2 V' = (Y'Y)^-1 and 1'Y_c = 0 (Y_c = Y - 1 mean(Y)'), that is
@@ -66,6 +66,18 @@ __global__ __launch_bounds__(64) void k_ucca_finish(const double *__restrict__ n
    res[j] = R;
    res[P_g + j] = F;
    res[2 * P_g + j] = P;
+}
+
+// fpca_debug_f_sf_dev: the device build of the F tail alone, one lane per r2, called as k_ucca_finish calls it
+__global__ __launch_bounds__(256) void k_f_sf(const double *__restrict__ r2, uint64_t count, uint64_t n, int k, double *__restrict__ F,
+                                              double *__restrict__ P)
+{
+   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+   if (i >= count) return;
+   double f, p;
+   ftail::f_sf(r2[i], n, k, &f, &p);
+   F[i] = f;
+   P[i] = p;
 }
 
 // Householder QR of the N x k column-major A (overwritten): the diagonal and upper triangle of R, k x k column-major
@@ -199,5 +211,22 @@ extern "C" int fpca_debug_f_sf(double r2, uint64_t n, int k, double *F, double *
    return guarded([&] {
       if (!F || !P || k < 1 || (uint64_t)k + 2 > n) throw Error(FPCA_EINVAL, "bad argument to fpca_debug_f_sf (needs k >= 1, n >= k + 2)");
       ftail::f_sf(r2, n, k, F, P);
+   });
+}
+
+extern "C" int fpca_debug_f_sf_dev(const double *r2, uint64_t count, uint64_t n, int k, double *F, double *P)
+{
+   return guarded([&] {
+      if (!F || !P || k < 1 || (uint64_t)k + 2 > n) throw Error(FPCA_EINVAL, "bad argument to fpca_debug_f_sf_dev (needs k >= 1, n >= k + 2)");
+      if (!count) return;
+      if (!r2) throw Error(FPCA_EINVAL, "bad argument to fpca_debug_f_sf_dev (NULL pointer)");
+      if (count > (uint64_t)1 << 31) throw Error(FPCA_EINVAL, "fpca_debug_f_sf_dev: more than 2^31 values");
+      DevMem<double> buf(3 * (size_t)count, "fpca_debug_f_sf_dev", "the values and their statistics");
+      double *dr2 = buf.p, *dF = dr2 + count, *dP = dF + count;
+      HIP_CHECK(hipMemcpy(dr2, r2, count * sizeof(double), hipMemcpyHostToDevice));
+      hipLaunchKernelGGL(k_f_sf, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, nullptr, dr2, count, n, k, dF, dP);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipMemcpy(F, dF, count * sizeof(double), hipMemcpyDeviceToHost)); // (the null stream: after the kernel)
+      HIP_CHECK(hipMemcpy(P, dP, count * sizeof(double), hipMemcpyDeviceToHost));
    });
 }

@@ -159,6 +159,14 @@ int fpca_debug_i8_instances(int32_t *keys, int cap, int *count);
  * involved): F = r2 / (1 - r2) (n - k - 1) / k and P = upper tail of F(k, n - k - 1) at F = I_{1 - r2}((n - k - 1) / 2, k / 2).
  * FPCA_EINVAL unless k >= 1 and n >= k + 2. */
 int fpca_debug_f_sf(double r2, uint64_t n, int k, double *F, double *P);
+/* diagnostic (tests/test_gpu_f_tail.py): the same from the DEVICE build, on the current device: one small kernel, one lane per value
+ * of r2[count], f_sf called as the finishing kernel of fpca_ucca calls it; F[count], P[count] out.  Refuses what fpca_debug_f_sf
+ * refuses; count = 0 returns at once. */
+int fpca_debug_f_sf_dev(const double *r2, uint64_t count, uint64_t n, int k, double *F, double *P);
+/* diagnostic (tests/test_gpu_scca_widths.py): the largest k fpca_scca_prepare accepts, the bytes of LDS the k-sized kernel of
+ * fpca_scca_fit needs at it (static arrays plus two vectors of k_pad doubles), and what `device` allows one workgroup
+ * (hipDeviceAttributeMaxSharedMemoryPerBlock): a property query, nothing is launched. */
+int fpca_debug_scca_lds(int device, int *max_k, int *need_at_max_k, int *per_workgroup);
 /* diagnostic (tests, scripts/cv_scca_measure.py): the one pass of fpca_scca_cv over the packed stream.  fold[N] in 0 .. nfolds - 1
  * (2 <= nfolds <= 64); counts (may be NULL): uint32 [nfolds][P_g][3], the samples of each fold with dosage 0, 1, 2 (the missing calls
  * are the fold's size minus the three); mean_sd (may be NULL): P_g x 2 like fpca_stats, the mean / sd over the samples OUTSIDE fold

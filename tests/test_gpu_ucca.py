@@ -1,6 +1,7 @@
 """fpca_ucca on the GPU against the reference's own arithmetic restated in numpy (RandomPCA::ucca, randompca.cpp:530-625: SVD of the
 standardised Y, cov, var, wilks) on the CPU oracle's standardised matrices: every --standy, chunked phenotype blocks, the missing-call
-routes and edge rules, the three arithmetics, SNP shards, the full-size problem, and the CLI end to end."""
+routes and edge rules, the three arithmetics, SNP shards, the full-size problem, the CLI end to end, and the finishing kernels at their
+edges: fewer SNPs than a row group, the ones column alone in and at column 1 of the third chunk, dense columns without variance."""
 import os
 import subprocess
 
@@ -229,3 +230,79 @@ def test_cli_end_to_end(fp, O, tmp_path):
         ml = [l.split("\t") for l in open(tmp_path / ("ms" + suffix)).read().splitlines()]
         assert ml[0] == ["SNP", "RefAllele", "Mean", "SD"]
         assert [x[2:] for x in ml[1:]] == [[O.format_number(v, prec) for v in m] for m in ms]
+
+
+def small_fileset(O, N, P, seed):
+    """Binomial dosages (MAF in [0.1, 0.5], 1 % missing calls, no monomorphic SNP) as packed records, and the oracle's dense matrix."""
+    rng = np.random.default_rng(seed)
+    maf = rng.uniform(0.1, 0.5, P)
+    u = rng.random((P, N))
+    codes = np.where(u < (maf * maf)[:, None], 0, np.where(u < (maf * (2 - maf))[:, None], 2, 3)).astype(np.uint8)  # hom A1, het, hom A2
+    codes[rng.random((P, N)) < 0.01] = 1  # missing
+    c = np.zeros((P, (N + 3) // 4 * 4), dtype=np.uint8)
+    c[:, :N] = codes
+    packed = (c[:, 0::4] | (c[:, 1::4] << 2) | (c[:, 2::4] << 4) | (c[:, 3::4] << 6)).astype(np.uint8)
+    X = O.OracleData(packed=packed, N=N, P=P, stand="binom2").dense()
+    assert np.all(X.std(axis=0) > 0)
+    return packed, X, rng
+
+
+@pytest.mark.parametrize("k", [1, 38])
+@pytest.mark.parametrize("P", [1, 15, 17])
+def test_fewer_snps_than_a_row_group(fp, O, P, k):
+    """k_ucca_accum takes 16 SNPs per workgroup and k_ucca_finish 64: one SNP, one short of a workgroup of the first, one over it.
+    N = 60 leaves n - k - 1 >= 21, so F stays well conditioned."""
+    N = 60
+    packed, X, rng = small_fileset(O, N, P, 100 * P + k)
+    Y = rng.standard_normal((N, k))
+    Ys, _ = O.standardise(Y, "sd")
+    with fp.Context.from_packed(packed, N, P, accum="auto") as ctx:
+        res = ctx.ucca(Y)
+    assert res.shape == (P, 3)
+    assert not compare(res, X, Ys, k, label="P=%d k=%d" % (P, k)).any()
+
+
+@pytest.mark.parametrize("k", [128, 129])
+def test_ones_column_in_the_third_chunk(fp, O, k):
+    """k + 1 columns in chunks of 64: the ones column alone in the third chunk (k = 128: no W column there, ncw = 0), then at column 1
+    of it behind the last W column (k = 129)."""
+    N, P = 200, 33
+    packed, X, rng = small_fileset(O, N, P, k)
+    Y = rng.standard_normal((N, k))
+    Ys, _ = O.standardise(Y, "sd")
+    with fp.Context.from_packed(packed, N, P, accum="auto") as ctx:
+        res = ctx.ucca(Y)
+    assert not compare(res, X, Ys, k, label="k=%d" % k).any()
+
+
+@pytest.mark.parametrize("stand", ["sd", "none"])
+def test_dense_columns_without_variance(fp, O, stand):
+    """The DEN_TOL rule of k_ucca_finish: a dense column whose sd is <= 1e-9 keeps its non-zero mean through the standardisation
+    (util.cpp:104-107), so its den = sum x^2 - (sum x)^2 / N is rounding noise of either sign, not 0: the row is NaN, NaN, NaN.
+    Two such columns: a constant one (3.7), and one that is NaN except for two equal values (0.1).  Under "none" the missing values
+    take the mean and both columns are constant: both rows NaN.  Under "sd" the missing values become 0 (util.cpp:102-103) and the two
+    observed ones do not: they keep the mean or, as here, the shifted-data variance of two equal values is rounding noise, sd = 3.9e-9
+    passes the 1e-9 test and they become (x - mean) / sd = -4e-9.  Either way the standardised column HAS variance, the reference's
+    loop on the standardised matrix gives it a finite row (R = 0.3104), and so must fpca_ucca: that row is held to the reference like
+    every other (a NaN there would be a departure from the reference, not an edge rule).  Every row not NaN by the rule is within compare()'s
+    bounds of the reference loop on the oracle's standardised matrix."""
+    N, P, k = 50, 20, 3
+    rng = np.random.default_rng(77)
+    Xr = rng.standard_normal((N, P)) * rng.uniform(0.5, 2, P) + rng.uniform(-1, 1, P)
+    Xr[rng.random((N, P)) < 0.02] = np.nan
+    const, two = 4, 11
+    Xr[:, const] = 3.7
+    Xr[:, two] = np.nan
+    Xr[[7, 31], two] = 0.1
+    Y = rng.standard_normal((N, k))
+    Ys, _ = O.standardise(Y, "sd")
+    Xs, _ = O.standardise(Xr, stand)
+    assert np.all(Xs[:, const] == Xs[0, const]) and Xs[0, const] != 0  # constant, non-zero mean kept
+    flat = [const, two] if stand == "none" else [const]
+    assert np.all(Xs[:, two] == 0.1) if stand == "none" else (len(set(Xs[:, two])) == 2 and np.sum(Xs[:, two] == 0) == N - 2)
+    with fp.Context.from_dense(Xr, stand=stand) as ctx:
+        res = ctx.ucca(Y)
+    assert res.shape == (P, 3)
+    assert np.all(np.isnan(res[flat])), res[flat]
+    others = np.setdiff1d(np.arange(P), flat)
+    assert not compare(res[others], Xs[:, others], Ys, k, label="dense " + stand).any()

@@ -74,6 +74,34 @@ def test_entry_points_declared_bound_and_exported(built_lib):
     assert all(hasattr(fp.Context, m) for m in ("scca_prepare", "scca_fit")) and callable(fp.scca)
 
 
+def test_the_limit_on_k_is_one_number_and_fits_the_lds(tmp_path):
+    """SCCA_MAX_K is written in scca.hpp, include/fpca.h, INTEGRATION.md and DESIGN.md: one number.  What it costs k_scca_v<1024> in LDS
+    -- the static part from the code object's metadata, 16 B per column of k_pad dynamic -- is the figure scca.hpp and the refusal's
+    message carry (tests/test_gpu_scca_widths.py holds it against the device's per-workgroup limit and runs the fit at the maximum)."""
+    csrc = os.path.join(ROOT, "flashpca_amd", "csrc")
+    hpp = open(os.path.join(csrc, "scca.hpp")).read()
+    max_k = int(re.search(r"constexpr int SCCA_MAX_K = (\d+);", hpp).group(1))
+    assert max_k % 16 == 0
+    assert "k > %d," % max_k in open(os.path.join(ROOT, "include", "fpca.h")).read()
+    assert "k > %s," % format(max_k, ",") in open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    assert "1 ≤ k ≤ %s " % format(max_k, ",") in design
+    out = str(tmp_path / "scca.s")
+    r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-S", os.path.join(csrc, "scca.hip"),
+                        "-o", out], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    txt = open(out).read()
+    static = {}
+    for block in txt.split("  - .agpr_count:")[1:]:
+        name = re.search(r"\.name:\s+(\S+)", block).group(1)
+        if "k_scca_v" in name:
+            static[re.search(r"k_scca_vILi(\d+)E", name).group(1)] = int(re.search(r"\.group_segment_fixed_size:\s+(\d+)", block).group(1))
+    assert static == {"256": 8 * (256 + 4), "1024": 8 * (1024 + 16)}, static
+    need = static["1024"] + 2 * 8 * max_k
+    assert "SCCA_V_LDS_MAX = 8 * (1024 + 16) + 2 * 8 * SCCA_MAX_K;" in hpp and "%s B at the maximum" % format(need, ",") in hpp
+    assert "%s B at the maximum" % format(need, ",") in design
+
+
 def test_cli_scca_still_refuses(built_lib, tmp_path):
     """The library has SCCA, the command line does not yet: wiring flashpca --scca is a follow-up, the flag keeps its
     refusal and its --help line."""

@@ -4,6 +4,7 @@ flashpca_amd.ucca()."""
 import ctypes as C
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -23,7 +24,8 @@ def f_sf(r2, n, k):
     return F.value, P.value
 
 
-R2_GRID = np.unique(np.concatenate([np.logspace(-12, -1e-4, 160), 1 - np.logspace(-12, -1, 60), np.linspace(0.005, 0.995, 100)]))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from f_tail_yardstick import KS, R2_GRID  # noqa: E402  (shared with tests/test_gpu_f_tail.py, which runs the device build on it)
 
 
 @pytest.mark.parametrize("n", [10, 957, 500000, 1000000])
@@ -45,6 +47,24 @@ def test_f_tail_matches_scipy(built_lib, n):
                 # (f.sf starts from F and forms 1 - x = k F / (n - k - 1 + k F) itself: at tiny r2 and large n that costs it digits)
                 Ps = stats.f.sf(F, k, n - k - 1)
                 assert abs(P - Ps) <= 1e-6 * Ps, (n, k, r2, P, Ps)
+                checked += 1
+            else:
+                assert 0.0 <= P < 1e-280, (n, k, r2, P, Pe)
+    assert checked > 300
+
+
+def test_f_tail_matches_scipy_at_one_residual_degree(built_lib):
+    """n = k + 2, the smallest n f_sf accepts (F(k, 1): a = 1/2), on the same grid at the same bounds."""
+    checked = 0
+    for k in KS:
+        n = k + 2
+        for r2 in R2_GRID:
+            F, P = f_sf(r2, n, k)
+            Fe = r2 / (1 - r2) * (n - k - 1) / k
+            assert abs(F - Fe) <= 1e-14 * Fe, (n, k, r2, F, Fe)
+            Pe = special.betaincc(k / 2.0, 0.5, r2)
+            if Pe >= 1e-290:
+                assert abs(P - Pe) <= 1e-8 * Pe, (n, k, r2, P, Pe)
                 checked += 1
             else:
                 assert 0.0 <= P < 1e-280, (n, k, r2, P, Pe)
