@@ -291,6 +291,63 @@ class Context:
         check(lib().fpca_bench_king(self.h, int(reps), _p(ms), C.byref(macs)))
         return ms, macs.value
 
+    def king_counts_block(self, i0, ni, j0, nj):
+        """fpca_king_counts_block: (counts, phi) of any rectangle of samples -- counts is the ni x nj x 6 uint32 array of (shared, ibs0,
+        hethet, het_i, het_j, D) per pair: the SNPs called in both samples, those at which they hold opposite homozygotes, those at which
+        both are heterozygous, and the sums phi is made of; phi is king_block's array, bit for bit."""
+        i0, ni, j0, nj = int(i0), int(ni), int(j0), int(nj)
+        if min(i0, ni, j0, nj) < 0:
+            raise ValueError("i0, ni, j0 and nj are non-negative")
+        counts = np.empty((max(ni, 1), max(nj, 1), 6), dtype=np.uint32)  # (a zero-sized request still reaches the library's refusal)
+        phi = np.empty((max(ni, 1), max(nj, 1)), dtype=np.float64)
+        check(lib().fpca_king_counts_block(self.h, i0, ni, j0, nj, _p(counts), _p(phi)))
+        return counts[:ni, :nj], phi[:ni, :nj]
+
+    def king_related(self, thr=0.0442, keep=None, min_shared=0, max_pairs=1 << 24, po_ibs0=0.005):
+        """fpca_king_related + fpca_king_classify: the relationship table of the pairs i < j with kinship phi > thr that share at least
+        min_shared called SNPs, among the samples of `keep` (None: all), sorted by (i, j) -- a dict of arrays with one entry per pair:
+        i, j, phi, shared, ibs0, hethet, het_i, het_j, dist (= D, the sum of squared dosage differences), ibs (PLINK's IBS similarity,
+        1 - (D - 2 ibs0) / (2 shared)) and type (0 unrelated, 1 parent-offspring, 2 full sibs, 3 second degree, 4 third degree, 5
+        duplicate / MZ, 255 no value; first degree is parent-offspring when ibs0 / shared < po_ibs0).  min_shared = 0 lists the pairs of
+        king_pairs.  FpcaError (code -4, the message names the count) when more than max_pairs qualify."""
+        k8 = self._sample_keep(keep)
+        max_pairs, min_shared = int(max_pairs), int(min_shared)
+        if max_pairs < 0:
+            raise ValueError("max_pairs is non-negative")
+        if not 0 <= min_shared <= 0xFFFFFFFF:
+            raise ValueError("min_shared is a count of SNPs between 0 and 2^32 - 1")
+        room = max(min(max_pairs, self.N * (self.N - 1) // 2), 1)
+        i = np.empty(room, dtype=np.uint32)
+        j = np.empty(room, dtype=np.uint32)
+        phi = np.empty(room, dtype=np.float64)
+        counts = np.empty((room, 6), dtype=np.uint32)
+        n = C.c_uint64(0)
+        check(lib().fpca_king_related(self.h, _p(k8), float(thr), min_shared, max_pairs, _p(i), _p(j), _p(phi), _p(counts), C.byref(n)))
+        return _king_table(i[:n.value].copy(), j[:n.value].copy(), phi[:n.value].copy(), counts[:n.value].copy(), po_ibs0)
+
+    def king_cutoff_shared(self, thr=0.0884, min_shared=0, keep=None):
+        """fpca_king_cutoff_shared: king_cutoff in which a pair that shares fewer than min_shared called SNPs counts as unrelated, whatever
+        its phi -- so that a poorly genotyped sample neither goes nor makes others go on the strength of a noisy coefficient.
+        min_shared = 0 gives king_cutoff's mask."""
+        k8 = self._sample_keep(keep)
+        if k8 is None:
+            k8 = np.ones(self.N, dtype=np.uint8)
+        min_shared = int(min_shared)
+        if not 0 <= min_shared <= 0xFFFFFFFF:
+            raise ValueError("min_shared is a count of SNPs between 0 and 2^32 - 1")
+        n = C.c_uint64(0)
+        check(lib().fpca_king_cutoff_shared(self.h, float(thr), min_shared, _p(k8), C.byref(n)))
+        out = k8 != 0
+        assert int(out.sum()) == n.value
+        return out
+
+    def bench_king_rel(self, reps=5):
+        """fpca_bench_king_rel: bench_king for the pair kernel of king_related."""
+        ms = np.zeros(int(reps), dtype=np.float64)
+        macs = C.c_double(0)
+        check(lib().fpca_bench_king_rel(self.h, int(reps), _p(ms), C.byref(macs)))
+        return ms, macs.value
+
     # ---- genotype census ------------------------------------------------------------------------------
     def snp_counts(self, samples=None):
         """fpca_snp_counts: the P x 4 uint32 array of genotype counts per SNP by raw .bed code (0 homozygous A1, 1 missing, 2 heterozygous,
@@ -705,7 +762,7 @@ def debug_i8_instances():
 
 def flashpca(X, ndim=10, stand="binom2", divisor="p", maxiter=500, tol=1e-6, do_loadings=False, return_scale=True,
              device=0, verbose=False, accum="auto", keep=None, snps=None, maf=0.0, geno=1.0, ld=None, unrelated=None,
-             mind=1.0, hwe=0.0, **solver_kw):
+             mind=1.0, hwe=0.0, unrelated_min_shared=0, **solver_kw):
     """PCA of a PLINK fileset; mirrors flashpca() of the reference's R package for the PLINK-prefix input
     (flashpcaR/R/flashpca.R:99-204 -> flashpca_plink_internal, flashpcaR/src/flashpca.cpp:96-197).
 
@@ -723,7 +780,8 @@ def flashpca(X, ndim=10, stand="binom2", divisor="p", maxiter=500, tol=1e-6, do_
     unrelated: a kinship threshold (0.0884: no pair closer than third degree).  PLINK input only.  After snps / maf / geno / ld -- which
     stay over all samples, the usual QC-then-KING order, and are allowed with it as long as keep is None -- Context.king_cutoff on the
     selected SNPs picks the samples (among those of keep=, if given), and the PCA runs on them as under keep=: the result gains
-    `unrelated_kept`, the mask over the samples, and `projection_all`.
+    `unrelated_kept`, the mask over the samples, and `projection_all`.  unrelated_min_shared: a pair that shares fewer called SNPs than
+    this is no relative, whatever its coefficient (Context.king_cutoff_shared); 0, the default, is king_cutoff itself.
     mind / hwe: PLINK's --mind (missing-call rate per sample <= mind) and --hwe (Hardy-Weinberg exact-test p-value per SNP >= hwe; no
     mid-p).  PLINK input only.  With either of them the order is: the snps list; mind, whose rate is over the listed SNPs and all samples
     (among the samples of keep=, if given); geno / hwe / maf over the samples mind left (Context.snp_qc_samples); ld, whose r2 stays over
@@ -795,7 +853,10 @@ def flashpca(X, ndim=10, stand="binom2", divisor="p", maxiter=500, tol=1e-6, do_
             keep = keep != 0
         unrelated_kept = None
         if unrelated is not None:
-            keep = unrelated_kept = ctx.king_cutoff(unrelated, keep=keep)
+            if unrelated_min_shared:
+                keep = unrelated_kept = ctx.king_cutoff_shared(unrelated, unrelated_min_shared, keep=keep)
+            else:
+                keep = unrelated_kept = ctx.king_cutoff(unrelated, keep=keep)
         if keep is not None:
             ctx.set_sample_mask(keep)
         r = ctx.pca(ndim=ndim, tol=tol, maxiter=maxiter, div=divisor, do_loadings=do_loadings, verbose=int(verbose),
@@ -1283,6 +1344,62 @@ def king_cutoff(prefix, thr=0.0884, snps=None, maf=0.0, geno=1.0, ld=None, keep=
             return full.king_cutoff(thr, keep=keep)
         with _select_snps(full, prefix, snps, qc, maf, geno, ld)[0] as sub:
             return sub.king_cutoff(thr, keep=keep)
+
+
+def king_classify(phi, counts, po_ibs0=0.005):
+    """fpca_king_classify (host only): the uint8 type of every pair from phi[n] and counts[n][6] -- see Context.king_related."""
+    phi = np.ascontiguousarray(phi, dtype=np.float64)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    if phi.ndim != 1 or counts.shape != (phi.size, 6):
+        raise ValueError("phi has one entry and counts six per pair; they have shapes %s and %s" % (phi.shape, counts.shape))
+    out = np.empty(phi.size, dtype=np.uint8)
+    check(lib().fpca_king_classify(phi.size, _p(phi), _p(counts), float(po_ibs0), _p(out)))
+    return out
+
+
+def _king_table(i, j, phi, counts, po_ibs0):
+    c = counts.astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ibs = 1.0 - (c[:, 5] - 2.0 * c[:, 1]) / (2.0 * c[:, 0])
+    return dict(i=i, j=j, phi=phi, shared=counts[:, 0].copy(), ibs0=counts[:, 1].copy(), hethet=counts[:, 2].copy(), het_i=counts[:, 3].copy(),
+                het_j=counts[:, 4].copy(), dist=counts[:, 5].copy(), ibs=ibs, type=king_classify(phi, counts, po_ibs0))
+
+
+def king_related(prefix, thr=0.0442, min_shared=0, po_ibs0=0.005, snps=None, maf=0.0, geno=1.0, ld=None, keep=None, device=0):
+    """The relationship table of a PLINK fileset (Context.king_related): every pair of rows i < j of prefix.fam with KING-robust kinship
+    above thr (0.0442: third degree and closer) that shares at least min_shared called SNPs, with the shared-SNP count, IBS0, het-het,
+    PLINK's IBS similarity and the inferred type (parent-offspring apart from full sibs by ibs0 / shared < po_ibs0).  snps / maf / geno /
+    ld as in king_cutoff(): applied first, over all samples.  keep: a boolean array with one entry per sample.  write_kin0() writes the
+    table in KING's .kin0 format.  Not byte-compatible with the KING binary."""
+    qc = not (maf <= 0 and geno >= 1)
+    if ld is not None:
+        ld = _ld_args(ld)
+    N = count_fam_rows(prefix + ".fam")
+    with Context.from_bed(prefix + ".bed", N, device=device, accum="fp64") as full:
+        if snps is None and not qc and ld is None:
+            return full.king_related(thr, keep=keep, min_shared=min_shared, po_ibs0=po_ibs0)
+        with _select_snps(full, prefix, snps, qc, maf, geno, ld)[0] as sub:
+            return sub.king_related(thr, keep=keep, min_shared=min_shared, po_ibs0=po_ibs0)
+
+
+def write_kin0(path, prefix, table):
+    """Write a king_related() table as KING's .kin0: a header and one tab-separated line per pair, FID1 ID1 FID2 ID2 N_SNP HetHet IBS0
+    Kinship -- family and individual IDs from the first two columns of prefix.fam, N_SNP = shared, HetHet and IBS0 as proportions of
+    N_SNP.  The three real columns are printed with %.17g, so they read back to the same doubles."""
+    ids = []
+    with open(prefix + ".fam") as f:
+        for line in f:
+            w = line.split()
+            if w:
+                ids.append((w[0], w[1]))
+    with open(path, "w") as f:
+        f.write("FID1\tID1\tFID2\tID2\tN_SNP\tHetHet\tIBS0\tKinship\n")
+        for i, j, n, hh, z, phi in zip(table["i"], table["j"], table["shared"], table["hethet"], table["ibs0"], table["phi"]):
+            i, j, n = int(i), int(j), int(n)
+            if max(i, j) >= len(ids):
+                raise ValueError("the table names sample %d; %s.fam has %d rows" % (max(i, j), prefix, len(ids)))
+            f.write("%s\t%s\t%s\t%s\t%d\t%.17g\t%.17g\t%.17g\n" % (ids[i] + ids[j] + (n, float(hh) / n if n else float("nan"),
+                                                                                float(z) / n if n else float("nan"), float(phi))))
 
 
 def project(X, loadings, orig_mean=None, orig_sd=None, ref_alleles=None, divisor="p", device=0, check_bim=True):

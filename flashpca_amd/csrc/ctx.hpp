@@ -24,6 +24,9 @@
 //                       (k_ld_band, six exact int8 products per pair), the --indep-pairwise rule on the host
 //   king.hip            fpca_king_block / fpca_king_pairs / fpca_king_cutoff: KING-robust kinship as the same Gram on a sample-major copy
 //                       (k_king, five products per pair; the loop itself is ld_planes.hpp), the greedy unrelated-sample rule on the host
+//   king_rel.hip        fpca_king_counts_block / fpca_king_related / fpca_king_cutoff_shared / fpca_king_classify: the relationship table --
+//                       shared calls, IBS0, het-het beside phi (k_king_rel, seven products per pair, a loop of its own), a minimum-shared
+//                       filter in front of king.hip's host rule, the degree / parent-offspring classification on the host
 //   qc_census.hip       fpca_snp_counts / fpca_sample_counts / fpca_hwe_exact / fpca_sample_qc / fpca_snp_qc_samples: genotype counts per SNP
 //                       over chosen samples (k_snp_counts) and per sample over chosen SNPs (k_sample_counts, a column census with vertical
 //                       counters), the HWE exact test (k_hwe_exact, one SNP per lane), the --mind and --geno / --maf / --hwe rules on the host

@@ -256,6 +256,40 @@ int fpca_king_block(fpca_ctx *ctx, uint64_t i0, uint64_t ni, uint64_t j0, uint64
 int fpca_king_pairs(fpca_ctx *ctx, const uint8_t *keep /* [N] or NULL */, double thr, uint64_t max_pairs, uint32_t *i, uint32_t *j, double *phi,
                     uint64_t *n_pairs);
 int fpca_king_cutoff(fpca_ctx *ctx, double thr, uint8_t *keep /* [N] in/out, like fpca_snp_qc */, uint64_t *n_kept);
+/*   The relationship table: beside phi, the integers KING's own table of a pair rests on.  With a0 = 1 at a homozygous-A2 call (dosage 0),
+ *   a2 = 1 at a homozygous-A1 call (dosage 2), over the SNPs called in BOTH samples:
+ *      shared = their number, ibs0 = sum a0_i a2_j + a2_i a0_j (opposite homozygotes), hethet = sum h_i h_j, het_i, het_j, D as above
+ *   A pair's counts are six uint32 in that order: shared, ibs0, hethet, het_i, het_j, D (het_i belongs to the first sample of the pair).
+ *   The device forms them from seven exact int8 products: ibs0 = (tt - ss) / 2 with tt = shared - het_i - het_j + hethet (both homozygous)
+ *   and ss = sum (x_i - m_i)(x_j - m_j) (+1 at equal, -1 at opposite homozygotes).  phi is formed as above and equals fpca_king_block /
+ *   fpca_king_pairs BIT FOR BIT.
+ *   fpca_king_counts_block   counts[ni][nj][6] and, when phi is not NULL, phi[ni][nj] for any rectangle, as fpca_king_block.  At i == j:
+ *                            shared = the sample's calls, ibs0 = 0, D = 0.  FPCA_EINVAL when counts would exceed 1 GiB.
+ *   fpca_king_related        fpca_king_pairs with a second condition and the counts: every pair i < j with phi > thr AND shared >=
+ *                            min_shared whose samples both have keep != 0, sorted by (i, j), in i[], j[], phi[], counts[][6] (max_pairs
+ *                            entries each); *n_pairs = their number.  min_shared = 0 lists exactly the pairs of fpca_king_pairs.  More
+ *                            than max_pairs: FPCA_ENOMEM, *n_pairs is the number needed, the arrays are not written.  FPCA_EINVAL when
+ *                            min(max_pairs, N (N - 1) / 2) entries of counts would exceed 1 GiB.
+ *   fpca_king_cutoff_shared  fpca_king_cutoff on the pairs of fpca_king_related (the same room, the same rule on the host): a pair that
+ *                            shares fewer than min_shared called SNPs is no edge.  min_shared = 0 gives exactly fpca_king_cutoff's mask.
+ *   fpca_king_classify       host only, no context: type[k] of pair k from phi[k] and counts[k][6] (shared and ibs0 are read).  In this order:
+ *                               255  no value: phi is NaN or shared == 0
+ *                                 5  duplicate / MZ twin: phi > 0.354
+ *                                 1  parent-offspring: 0.177 < phi <= 0.354 and (double)ibs0 / (double)shared < po_ibs0
+ *                                 2  full sibs: 0.177 < phi <= 0.354 otherwise
+ *                                 3  second degree: 0.0884 < phi <= 0.177
+ *                                 4  third degree: 0.0442 < phi <= 0.0884
+ *                                 0  unrelated
+ *                            FPCA_EINVAL for a NULL array with n_pairs > 0 and a po_ibs0 that is NaN, infinite or negative.  The cut
+ *                            points are KING's (2^-1.5, 2^-2.5, ... rounded as its manual prints them); po_ibs0 is a convention of the
+ *                            caller (the Python layer passes 0.005).  Parity with the KING binary's inference is not claimed.
+ *   The three device calls refuse what the calls above refuse, make the same sample-major copy and leave the context unchanged. */
+int fpca_king_counts_block(fpca_ctx *ctx, uint64_t i0, uint64_t ni, uint64_t j0, uint64_t nj, uint32_t *counts /* [ni][nj][6] */,
+                           double *phi /* [ni][nj] or NULL */);
+int fpca_king_related(fpca_ctx *ctx, const uint8_t *keep /* [N] or NULL */, double thr, uint32_t min_shared, uint64_t max_pairs, uint32_t *i,
+                      uint32_t *j, double *phi, uint32_t *counts /* [max_pairs][6] */, uint64_t *n_pairs);
+int fpca_king_cutoff_shared(fpca_ctx *ctx, double thr, uint32_t min_shared, uint8_t *keep /* [N] in/out */, uint64_t *n_kept);
+int fpca_king_classify(uint64_t n_pairs, const double *phi, const uint32_t *counts /* [n_pairs][6] */, double po_ibs0, uint8_t *type /* [n_pairs] */);
 
 /* Genotype census: counts per SNP over a chosen set of samples, counts per sample over a chosen set of SNPs, the Hardy-Weinberg exact test
  * on such counts, and the two QC rules on top of them -- PLINK's --mind (per-sample call rate) and --geno / --maf / --hwe over the KEPT

@@ -199,6 +199,9 @@ int fpca_debug_king_rule(const uint32_t *i, const uint32_t *j, uint64_t n_pairs,
  * triangle) with a pair of HIP events around each, ms[reps].  *macs (may be NULL): int8 multiply-accumulates one pass issues (32 x 32 x
  * 32 per MFMA, pad SNPs included). */
 int fpca_bench_king(fpca_ctx *ctx, int reps, double *ms, double *macs);
+/* the same for the pair kernel of fpca_king_related (scripts/king_rel_measure.py), at thr = 0.0884, min_shared = 0, no keep: seven
+ * products per pair of 32-sample blocks on the general path, two where neither block has a missing call. */
+int fpca_bench_king_rel(fpca_ctx *ctx, int reps, double *ms, double *macs);
 /* diagnostic (tests): the rules of fpca_sample_qc / fpca_snp_qc_samples on caller arrays, no context and no device involved.  counts:
  * uint32 [N][4] / [P][4] by raw code; n_snps: the SNPs the per-sample counts were taken over; n: the samples the per-SNP counts were taken
  * over; p_hwe[P]: the p-values, read only when min_hwe_p > 0 (may be NULL otherwise); samples[N] / keep[P] in and out.  FPCA_EINVAL for
