@@ -21,6 +21,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 #include <utility>
 
@@ -492,11 +493,16 @@ __device__ __forceinline__ v4i lds_read16(uint32_t addr) // explicit LDS read: t
    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
    return r;
 }
-template <int OFF>
+// NT: the load carries the `nt` bit -- served from L2 like any other, but its line is not kept in the CU's L1 on the way through (for a
+// stream that a CU reads once: the packed words, I8Nt).  It counts in vmcnt like a plain load.
+template <int OFF, bool NT = false>
 __device__ __forceinline__ u4 gload16(const void *sbase, uint32_t voff) // explicit global load, address = sbase + voff + OFF
 {
    u4 r;
-   asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(r) : "v"(voff), "s"(sbase), "n"(OFF));
+   if constexpr (NT)
+      asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3 nt" : "=v"(r) : "v"(voff), "s"(sbase), "n"(OFF));
+   else
+      asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(r) : "v"(voff), "s"(sbase), "n"(OFF));
    return r;
 }
 __device__ __forceinline__ u2 gload8(const void *sbase, uint32_t voff) // ... 8 bytes, address = sbase + voff
@@ -555,6 +561,7 @@ enum { I8_FULL = 0, I8_SKIP_EMPTY = 1, I8_NO_MISSING = 2 };
 template <bool TWO_, int MT_, int NT_, int WR_, int WC_, int KC_, int G_, int MODE_ = I8_FULL, bool HALF_ = false, bool TILED_ = false>
 struct I8Cfg {
    static constexpr bool TWO = TWO_, HALF = HALF_, TILED = TILED_;
+   static constexpr bool NT_P = false; // load policy of the packed words (issue_p): plain here, `nt` in the twin I8Nt makes of an instance
    static_assert(!TILED || KC_ == 256, "the band-tiled layout is cut in chunks of 256 codes");
    static constexpr int MT = MT_, NT = NT_, WR = WR_, WC = WC_, KC = KC_, G = G_, NQ = TWO ? 2 : 1, MODE = MODE_;
    static constexpr int MATS = MODE == I8_NO_MISSING ? 1 : 2;
@@ -599,6 +606,17 @@ struct I8Cfg {
    static constexpr int LDS_BYTES = (!TWO && NT <= 2 && WAVES == 4 && LDS_NEED < 56 * 1024) ? 56 * 1024 : LDS_NEED;
    static_assert((HALF8 ? (COLS - 16) % RSTEP == 0 && KC == 256 : COLS % RSTEP == 0) && NSTEP % 2 == 0 && LDS_BYTES <= 160 * 1024, "staging");
    static_assert(!HALF || RSTEP == 16 || HALF8, "the remainder tile is the last staging piece");
+};
+
+// The twin of instance C whose packed-word loads bypass L1: every packed byte is decoded by one lane of one wave, once per launch, and
+// since the band tiling every line of the stream is requested once -- nothing of it is ever found in L1 again.  Same registers, same
+// order of loads and waits, same bits.  (A wrapper and not one more argument of I8Cfg: the plain instances keep their names.)
+// Measured at cfg3 (profiles/load_policy_ab.txt): the apply 10.26 -> 10.21 ms, the 4-slice apply 7.52 -> 7.40 ms, every run of six below
+// every run of the parent.  The same bit on the operand pieces (staged once per workgroup, shared between CUs in L2) LOSES 0.17 / 0.82 ms,
+// on the rows the missing-call gathers fetch 0.65 / 0.73 ms: neither is kept.
+template <class C>
+struct I8Nt : C {
+   static constexpr bool NT_P = true;
 };
 
 // returns (MODE == I8_SKIP_EMPTY) whether any lane of the wave holds a missing genotype in this 32-row x 32-k block
@@ -719,8 +737,8 @@ __global__ __launch_bounds__(C::THREADS, 1) void k_gemm_i8(const uint8_t *__rest
       const uint8_t *pb = prow + (size_t)cc * (C::TILED ? 2048 : KC / 4);
 #pragma unroll
       for (int m = 0; m < MT; m++) {
-         dst[m][0] = gload16<0>(pb, pvoff[m]);
-         if constexpr (PW == 2) dst[m][1] = gload16<(C::TILED ? 1024 : 16)>(pb, pvoff[m]);
+         dst[m][0] = gload16<0, C::NT_P>(pb, pvoff[m]);
+         if constexpr (PW == 2) dst[m][1] = gload16<(C::TILED ? 1024 : 16), C::NT_P>(pb, pvoff[m]);
       }
    };
    auto store_q = [&](auto rr, unsigned char *st, auto behind) { // `behind`: loads issued after the NP pieces (the packed words, or none)
@@ -1136,31 +1154,42 @@ using I8Instances = I8List<
    I8Both<2, I8_FULL>, I8Both<3, I8_FULL>, I8Both<4, I8_FULL>, I8Both<5, I8_FULL>, I8Both<6, I8_FULL>, I8Both<7, I8_FULL>, I8Both<8, I8_FULL>,
    I8Both<4, I8_FULL, I8_HALF>,
    I8Both<2, I8_SKIP_EMPTY>, I8Both<3, I8_SKIP_EMPTY>, I8Both<4, I8_SKIP_EMPTY>, I8Both<5, I8_SKIP_EMPTY>, I8Both<6, I8_SKIP_EMPTY>,
-   I8Both<7, I8_SKIP_EMPTY>, I8Both<8, I8_SKIP_EMPTY>>;
+   I8Both<7, I8_SKIP_EMPTY>, I8Both<8, I8_SKIP_EMPTY>,
+   // the L1-bypassing twins (I8Nt) of what the headline and the cheap pass launch: G.M alone, band-tiled, 3.5 tiles at 512 and 256 rows
+   // and 2 tiles at 256 rows
+   I8Nt<I8One<4, I8_TL, I8_HALF, 8>>, I8Nt<I8One<4, I8_TL, I8_HALF>>, I8Nt<I8One<2, I8_TL>>>;
 
-// what tells two instances apart: the operands, the matrices, the column block, the tile height and the layout of `packed`
+// what tells two instances apart: the operands, the matrices, the column block, the tile height, the layout of `packed` and the policy
+// of its loads
 struct I8Key {
    bool two;
    int mode, nt;
    bool half;
    int rows;
    bool tiled;
+   bool nt_p = false;
 };
 // f(C{}) for the instance C with this key, and its answer; false if there is none
 template <class... C, class F>
 constexpr bool i8_find(I8List<C...>, const I8Key &k, F &&f)
 {
-   return ((k.two == C::TWO && k.mode == C::MODE && k.nt == C::NT && k.half == C::HALF && k.rows == C::ROWS && k.tiled == C::TILED && f(C{})) || ...);
+   return ((k.two == C::TWO && k.mode == C::MODE && k.nt == C::NT && k.half == C::HALF && k.rows == C::ROWS && k.tiled == C::TILED &&
+            k.nt_p == C::NT_P && f(C{})) || ...);
 }
-// the key of every member of the list, in the list's order (fpca_debug_i8_instances: what a census of the launched instances is held to)
+// the key of every member of the list, in the list's order (fpca_debug_i8_instances: what a census of the launched instances is held to).
+// The L1-bypassing twins are not listed: they share their plain twin's six numbers, and tests/test_gpu_load_policy.py launches each
 template <class... C>
 static int i8_keys(I8List<C...>, int (*out)[6], int cap)
 {
-   const I8Key keys[] = {I8Key{C::TWO, C::MODE, C::NT, C::HALF, C::ROWS, C::TILED}...};
-   const int n = (int)sizeof...(C);
-   for (int i = 0; i < n && i < cap; i++) {
-      const int k[6] = {keys[i].two, keys[i].mode, keys[i].nt, keys[i].half, keys[i].rows, keys[i].tiled};
-      std::copy(k, k + 6, out[i]);
+   const I8Key keys[] = {I8Key{C::TWO, C::MODE, C::NT, C::HALF, C::ROWS, C::TILED, C::NT_P}...};
+   int n = 0;
+   for (const I8Key &key : keys) {
+      if (key.nt_p) continue;
+      if (n < cap) {
+         const int k[6] = {key.two, key.mode, key.nt, key.half, key.rows, key.tiled};
+         std::copy(k, k + 6, out[n]);
+      }
+      n++;
    }
    return n;
 }
@@ -1232,6 +1261,18 @@ static int i8_tile_rows(uint64_t rows_pad, int ncu, const I8Shape &sh)
    }
    const uint64_t tiles512 = (rows_pad + 511) / 512;
    return (sh.half && sh.nt == 4 && tiles512 * 4 >= (uint64_t)I8_WIDE_QUARTERS * ncu) ? 512 : sh.rows;
+}
+
+// Load policy of one launch: the packed words bypass L1 wherever the instance has a twin that does (I8Nt).  The e_only launches on the
+// hybrid route's compacted records stay plain, and so does every instance without a twin.  FPCA_I8_LOADS=plain|p (test builds) forces
+// the choice wherever a twin exists.
+static bool i8_nt_p(I8Key k, bool e_only)
+{
+   static const char *env_l = FPCA_TEST_ENV("FPCA_I8_LOADS");
+   if (env_l && std::strcmp(env_l, "p") && std::strcmp(env_l, "plain")) throw Error(-1, "FPCA_I8_LOADS is plain or p");
+   if (e_only || (env_l && !std::strcmp(env_l, "plain"))) return false;
+   k.nt_p = true;
+   return i8_find(I8Instances{}, k, [](auto) { return true; });
 }
 
 // the 4-wave shape, whatever the launch and the device
@@ -1415,9 +1456,11 @@ void gemm_i8(const uint8_t *packed, size_t pitch, const int8_t *Qg, const int8_t
    const I8Plan pl = i8_plan(rows_pad, k_pad, sh, bw);
    const int chunks_total = (int)(k_pad / sh.kc);
    // (the plan line above is printed for the workspace sizing too: this one marks the plan that is launched, and the instance)
+   const bool nt_p = i8_nt_p(I8Key{two, mode, sh.nt, sh.half, sh.rows, tiled}, e_only);
    if (i8_verbose())
-      std::fprintf(stderr, "[fpca] int8 GEMM launch: %s, mode %d, nt %d%s, %s%s; phase B from row %llu\n", two ? "two operands" : "one operand", mode,
-                   sh.nt, sh.half ? " (half tile)" : "", tiled ? "band-tiled" : "row-major", e_only ? ", E alone" : "", (unsigned long long)pl.rowB0);
+      std::fprintf(stderr, "[fpca] int8 GEMM launch: %s, mode %d, nt %d%s, %s%s; phase B from row %llu; rows %d, loads %s\n", two ? "two operands" : "one operand", mode,
+                   sh.nt, sh.half ? " (half tile)" : "", tiled ? "band-tiled" : "row-major", e_only ? ", E alone" : "", (unsigned long long)pl.rowB0,
+                   sh.rows, nt_p ? "p" : "plain");
    // FPCA_DEBUG_I8_POISON (test builds): NaNs in exactly the extent of the workspace this plan uses -- plane 0 of every row, planes
    // 1 .. sB-1 of the phase-B rows -- so that a partial the kernel fails to write cannot pass for the previous launch's value
    static const bool poison = FPCA_TEST_ENV("FPCA_DEBUG_I8_POISON") != nullptr;
@@ -1429,7 +1472,7 @@ void gemm_i8(const uint8_t *packed, size_t pitch, const int8_t *Qg, const int8_t
    if (two && mode == I8_NO_MISSING) throw Error(-1, "gemm_i8: without missing genotypes both matrices share one operand (pass Qm == Qg)");
    // the instance of this shape at the tile height chosen for these rows, for the layout of `packed`: plan, kernel and combine then
    // walk the same tile grid
-   const bool launched = i8_find(I8Instances{}, I8Key{two, mode, sh.nt, sh.half, sh.rows, tiled}, [&](auto c) {
+   const bool launched = i8_find(I8Instances{}, I8Key{two, mode, sh.nt, sh.half, sh.rows, tiled, nt_p}, [&](auto c) {
       using C = decltype(c);
       if (C::COLS != sh.cols || C::KC != sh.kc) throw Error(-1, "gemm_i8: the kernel instance and the shape disagree about the tile");
       launch_i8<C>(pl, stream, packed, pitch, Qg, Qm, k_pad, wg, wm, bw, ws, rows_pad, chunks_total, sh.zb, (e_only ? 0x00000100u : 0x00010002u));
