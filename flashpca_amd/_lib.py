@@ -184,6 +184,7 @@ SIGNATURES = {
     "fpca_debug_i8_nsc_pad": (_I, [_I, _I, C.POINTER(_I)]),
     "fpca_debug_i8_slices": (_I, [_I, _I, _I, _U64, _U64, _U64, _P, _P, _P, _P, _I, C.POINTER(SlicesOut), C.POINTER(SlicesOut), C.POINTER(_I)]),
     "fpca_debug_i8_instances": (_I, [_P, _I, C.POINTER(_I)]),
+    "fpca_debug_gather_blocks": (_I, [_I, _I, _I, _I, _I, _U64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "fpca_debug_f_sf":(_I, [_D, _U64, _I, C.POINTER(_D), C.POINTER(_D)]),
     "fpca_debug_f_sf_dev": (_I, [_P, _U64, _U64, _I, _P, _P]),
     "fpca_debug_scca_lds": (_I, [_I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),

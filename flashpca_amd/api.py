@@ -760,6 +760,16 @@ def debug_i8_instances():
     return [(bool(k[0]), int(k[1]), int(k[2]), bool(k[3]), int(k[4]), bool(k[5])) for k in keys[:n.value]]
 
 
+def debug_gather_blocks(gemm_waves, gemm_vgprs, gemm_lds, gather_vgprs, ncu, rows_out=1 << 30):
+    """fpca_debug_gather_blocks: the grid of a side-stream gather beside a GEMM whose workgroup has gemm_waves waves, gemm_vgprs registers per
+    lane and gemm_lds bytes of LDS, for a gather kernel of gather_vgprs registers on ncu CUs; host only.  Returns (the block limit, the
+    grid of a side-stream launch over rows_out rows, the grid of an inline one)."""
+    lim, side, inline = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    check(lib().fpca_debug_gather_blocks(int(gemm_waves), int(gemm_vgprs), int(gemm_lds), int(gather_vgprs), int(ncu), int(rows_out),
+                                         C.byref(lim), C.byref(side), C.byref(inline)))
+    return lim.value, side.value, inline.value
+
+
 def flashpca(X, ndim=10, stand="binom2", divisor="p", maxiter=500, tol=1e-6, do_loadings=False, return_scale=True,
              device=0, verbose=False, accum="auto", keep=None, snps=None, maf=0.0, geno=1.0, ld=None, unrelated=None,
              mind=1.0, hwe=0.0, unrelated_min_shared=0, **solver_kw):

@@ -473,6 +473,20 @@ int fpca_debug_i8_instances(int32_t *keys, int cap, int *count)
    });
 }
 
+int fpca_debug_gather_blocks(int gemm_waves, int gemm_vgprs, int gemm_lds, int gather_vgprs, int ncu, uint64_t rows_out, uint32_t *limit,
+                             uint32_t *grid_side, uint32_t *grid_inline)
+{
+   return guarded([&] {
+      if (!limit || !grid_side || !grid_inline) throw Error(FPCA_EINVAL, "fpca_debug_gather_blocks: an output is NULL");
+      if (gemm_waves < 1 || gemm_waves > 16 || gemm_vgprs < 1 || gemm_vgprs > 512 || gather_vgprs < 1 || gather_vgprs > 512 || gemm_lds < 0 ||
+          gemm_lds > 160 * 1024 || ncu < 1 || ncu > 4096 || rows_out < 1)
+         throw Error(FPCA_EINVAL, "bad argument to fpca_debug_gather_blocks");
+      *limit = kern::gather_blocks_beside(kern::CuFootprint{gemm_waves, gemm_vgprs, gemm_lds}, gather_vgprs, ncu);
+      *grid_side = kern::sparse_rows_sum_grid(rows_out, *limit);
+      *grid_inline = kern::sparse_rows_sum_grid(rows_out, 0);
+   });
+}
+
 int fpca_debug_i8_slices(int route, int b, int S, uint64_t rows, uint64_t rows_pad, uint64_t rows_valid, const double *V, const double *rowscale0,
                          const double *rowscale1, const double *peers, int n_peers, fpca_debug_slices_out *out0, fpca_debug_slices_out *out1,
                          int *nsc_pad)

@@ -155,6 +155,12 @@ int gemm_i8_nsc_pad(int S, int b); // rows of a Q operand: S*b rounded up to the
 size_t gemm_i8_workspace_doubles(uint64_t rows_pad, uint64_t k_pad, int S, int b, bool two);
 // every k_gemm_i8 instance there is as (two operands, mode, nt, half tile, tile rows, band-tiled): writes min(count, cap), returns the count
 int gemm_i8_instances(int (*out)[6], int cap);
+// what one workgroup of a kernel holds of a CU: its waves, the registers of a lane (VGPRs + AGPRs, as the compiler asks for them) and its LDS
+struct CuFootprint {
+   int waves, vgprs, lds_bytes;
+};
+// of the k_gemm_i8 instance gemm_i8 launches for these arguments (the registers from the loaded code object, asked once per instance)
+CuFootprint gemm_i8_footprint(uint64_t rows_pad, int S, int b, bool two, int mode, bool e_only, bool tiled);
 // out[rows_pad][b] = recombined ( (G.M) Qg' , M Qm' ); mean/sd non-null: K2 flavour (per-row standardisation)
 void gemm_i8(const uint8_t *packed, size_t pitch, const int8_t *Qg, const int8_t *Qm, const double *wg, const double *wm,
              const long long *colsum_m, const double *mean, const double *sd, double *out, double *ws, uint64_t rows_pad, uint64_t k_pad,
@@ -187,14 +193,27 @@ void fill_missing(const uint8_t *packed, size_t pitch, uint64_t ncols, uint64_t 
 void sparse_rows_sum(const uint32_t *ptr, const uint32_t *idx, const double *V, const double *rowscale, int b, uint64_t nrec,
                      uint64_t rows_out, double *out, hipStream_t stream, const double *init = nullptr /* [rows_out][b] added to the sums */,
                      bool short_lists = false /* many short lists (per sample): the batched index reads */,
-                     double avg_len = 0 /* entries per list, if known: a dozen or so takes the several-rows-per-wave kernel */);
+                     double avg_len = 0 /* entries per list, if known: a dozen or so takes the several-rows-per-wave kernel */,
+                     unsigned block_limit = 0 /* most blocks of the one-wave-per-row kernels (sparse_rows_sum_blocks_beside); 0: no limit */);
 // the same over the fp32 rows k_slice leaves (SliceOp::copy32: each column scaled into (-2, 2) by its slice exponent; colw = that
 // operand's slice weights, which carry the exponent back)
 void sparse_rows_sum_f32(const uint32_t *ptr, const uint32_t *idx, const float *V, const double *colw, int b, uint64_t nrec, uint64_t rows_out,
-                         double *out, hipStream_t stream, const double *init = nullptr, bool short_lists = false, double avg_len = 0);
+                         double *out, hipStream_t stream, const double *init = nullptr, bool short_lists = false, double avg_len = 0,
+                         unsigned block_limit = 0);
 // which kernel the two launches above take for these arguments (rowscale: a per-row factor is given): 1 one wave per row, 2 the same
 // with batched index reads, 3 several rows per wave
 int sparse_rows_sum_variant(int b, bool rowscale, bool short_lists, double avg_len);
+// The grid of a gather that runs on the side stream beside a GEMM: as many 256-thread blocks (a wave per SIMD) as stay resident on `ncu`
+// CUs next to the workgroups of `gemm` that share a CU -- what is left of the 8 wave slots and 512 registers of a SIMD (allocated in
+// eights).  Such a grid is placed once and queues nothing: a CU that a GEMM workgroup leaves is not refilled with gather blocks before
+// the next one arrives.  At least one block per CU, also where nothing is left.  Pure: no device involved.
+unsigned gather_blocks_beside(const CuFootprint &gemm, int gather_vgprs, int ncu);
+// blocks of a launch of the one-wave-per-row kernels over rows_out rows: four rows a block up to 65536 blocks, and no more than
+// block_limit (0: no limit -- an inline launch)
+unsigned sparse_rows_sum_grid(uint64_t rows_out, unsigned block_limit);
+// ... for the kernel sparse_rows_sum / sparse_rows_sum_f32 take for these arguments, on the current device; 0 (no limit) for the
+// several-rows-per-wave kernel, whose lists are too short to be worth a side stream
+unsigned sparse_rows_sum_blocks_beside(const CuFootprint &gemm, int b, bool f32, bool rowscale, bool short_lists, double avg_len);
 
 } // namespace kern
 } // namespace fpca

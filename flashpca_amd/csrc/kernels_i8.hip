@@ -1438,6 +1438,26 @@ static void launch_i8(const I8Plan &pl, hipStream_t stream, const uint8_t *packe
                       ws, rows_pad, chunks_total, zb, pl.nA, pl.sB, pl.cpsB, pl.rowB0, pl.rowsB, tab1);
 }
 
+CuFootprint gemm_i8_footprint(uint64_t rows_pad, int S, int b, bool two, int mode, bool e_only, bool tiled)
+{
+   const I8Shape sh = i8_shape(S, b, two, mode, rows_pad);
+   const bool nt_p = i8_nt_p(I8Key{two, mode, sh.nt, sh.half, sh.rows, tiled}, e_only);
+   CuFootprint f{0, 0, 0};
+   i8_find(I8Instances{}, I8Key{two, mode, sh.nt, sh.half, sh.rows, tiled, nt_p}, [&](auto c) {
+      using C = decltype(c);
+      static int regs = 0; // (one per instance)
+      if (!regs) {
+         hipFuncAttributes attr;
+         // unknown: as if a lane held half a SIMD's registers, which leaves a gather its one block per CU
+         regs = hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&k_gemm_i8<C>)) == hipSuccess && attr.numRegs > 0 ? attr.numRegs : 256;
+      }
+      f = CuFootprint{C::WAVES, regs, C::LDS_BYTES};
+      return true;
+   });
+   if (!f.waves) throw Error(-1, "gemm_i8: no kernel instance for this shape");
+   return f;
+}
+
 void gemm_i8(const uint8_t *packed, size_t pitch, const int8_t *Qg, const int8_t *Qm, const double *wg, const double *wm,
              const long long *colsum_m, const double *mean, const double *sd, double *out, double *ws, uint64_t rows_pad, uint64_t k_pad,
              uint64_t rows_valid, int mode, const double *eplane /* I8_NO_MISSING kernel + E'Q computed elsewhere, or null */, int b,

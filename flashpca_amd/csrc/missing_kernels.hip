@@ -4,7 +4,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
+#include <map>
+#include <mutex>
 
 #include "common.hpp"
 #include "kernels.hpp"
@@ -331,13 +334,77 @@ int sparse_rows_sum_variant(int b, bool rowscale, bool short_lists, double avg_l
    return variant == 1 ? 1 : 2;
 }
 
+unsigned gather_blocks_beside(const CuFootprint &gemm, int gather_vgprs, int ncu)
+{
+   constexpr int SIMDS = 4, WAVE_SLOTS = 8, VGPRS = 512, LDS = 160 * 1024; // of a CU: SIMDs, waves and registers of a SIMD, bytes of LDS
+   const auto alloc = [](int r) { return (std::max(r, 1) + 7) / 8 * 8; };
+   const int wps = std::max((gemm.waves + SIMDS - 1) / SIMDS, 1), regs = alloc(gemm.vgprs) * wps; // of one GEMM workgroup per SIMD
+   // the GEMM's workgroups that share a CU (the 3.5-tile 8-wave instance: one, by its LDS; the 2-tile 4-wave one: two)
+   const int wgs = std::max(std::min({WAVE_SLOTS / wps, VGPRS / regs, gemm.lds_bytes > 0 ? LDS / gemm.lds_bytes : WAVE_SLOTS}), 1);
+   const int slots = WAVE_SLOTS - wgs * wps, left = VGPRS - wgs * regs;
+   const int per_cu = std::min(slots, left / alloc(gather_vgprs));
+   return (unsigned)std::max(per_cu, 1) * (unsigned)std::max(ncu, 1);
+}
+
+// The one-wave-per-row kernels walk the rows in a grid-stride loop, a wave a row: a smaller grid changes no sum.
+unsigned sparse_rows_sum_grid(uint64_t rows_out, unsigned block_limit)
+{
+   const unsigned blocks = (unsigned)std::min<uint64_t>(65536, (rows_out + 3) / 4);
+   return block_limit ? std::min(blocks, block_limit) : blocks;
+}
+
+// the kernel of (variant 1 / 2, b, VT), for its attributes
+template <class VT>
+static const void *sparse_rows_sum_kernel(int variant, int b)
+{
+#define FPCA_GATHER_FN(B_) (variant == 1 ? reinterpret_cast<const void *>(&k_sparse_rows_sum<B_, VT>) : reinterpret_cast<const void *>(&k_sparse_rows_sum_batched<B_, VT>))
+   return b == 16 ? FPCA_GATHER_FN(16) : b == 32 ? FPCA_GATHER_FN(32) : b == 64 ? FPCA_GATHER_FN(64) : nullptr;
+#undef FPCA_GATHER_FN
+}
+
+unsigned sparse_rows_sum_blocks_beside(const CuFootprint &gemm, int b, bool f32, bool rowscale, bool short_lists, double avg_len)
+{
+   const int variant = sparse_rows_sum_variant(b, rowscale, short_lists, avg_len);
+   if (variant == 3) return 0;
+   const void *fn = f32 ? sparse_rows_sum_kernel<float>(variant, b) : sparse_rows_sum_kernel<double>(variant, b);
+   if (!fn) throw Error(-1, "sparse_rows_sum: block width must be 16, 32 or 64");
+   // asked once per kernel (this runs in every apply); the devices of one process are alike
+   static std::mutex mtx;
+   static std::map<const void *, int> regs_of;
+   static int ncu = 0;
+   std::lock_guard<std::mutex> lock(mtx);
+   auto it = regs_of.find(fn);
+   if (it == regs_of.end()) {
+      hipFuncAttributes attr;
+      if (hipFuncGetAttributes(&attr, fn) != hipSuccess || attr.numRegs <= 0) throw Error(-3, "sparse_rows_sum: the gather kernel's registers could not be read");
+      it = regs_of.emplace(fn, attr.numRegs).first;
+   }
+   if (!ncu) {
+      int dev = 0;
+      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) {
+         ncu = 0;
+         throw Error(-3, "sparse_rows_sum: the device's CU count could not be read");
+      }
+   }
+   return gather_blocks_beside(gemm, it->second, ncu);
+}
+
 template <class VT>
 static void sparse_rows_sum_t(const uint32_t *ptr, const uint32_t *idx, const VT *V, const double *rowscale, int b, uint64_t nrec,
-                              uint64_t rows_out, double *out, hipStream_t stream, const double *init, bool short_lists, const double *colw, double avg_len)
+                              uint64_t rows_out, double *out, hipStream_t stream, const double *init, bool short_lists, const double *colw, double avg_len,
+                              unsigned block_limit)
 {
    if (!rows_out) return;
-   const unsigned blocks = (unsigned)std::min<uint64_t>(65536, (rows_out + 3) / 4);
+   // FPCA_GATHER_BLOCKS (test builds, read on every call) replaces the limit on every launch, inline ones too, for the tests and for
+   // A/B runs: a number of blocks, 0 for no limit
+   if (const char *env_b = FPCA_TEST_ENV("FPCA_GATHER_BLOCKS")) {
+      if (atoi(env_b) < 0) throw Error(-1, "FPCA_GATHER_BLOCKS is a number of blocks (0: no limit)");
+      block_limit = (unsigned)atoi(env_b);
+   }
+   const unsigned blocks = sparse_rows_sum_grid(rows_out, block_limit);
    const int variant = sparse_rows_sum_variant(b, rowscale != nullptr, short_lists, avg_len);
+   if (FPCA_TEST_ENV("FPCA_GATHER_VERBOSE")) // (test builds: what the tests hold the grid to; the several-rows-per-wave kernel has its own grid)
+      std::fprintf(stderr, "[fpca] gather launch: kernel %d, %llu rows, %u blocks, limit %u\n", variant, (unsigned long long)rows_out, blocks, block_limit);
 #define FPCA_GATHER_CASE(B_)                                                                                                    \
    case B_:                                                                                                                     \
       if (variant == 3 && B_ <= 32) {                                                                                           \
@@ -358,14 +425,14 @@ static void sparse_rows_sum_t(const uint32_t *ptr, const uint32_t *idx, const VT
    launch_check();
 }
 void sparse_rows_sum(const uint32_t *ptr, const uint32_t *idx, const double *V, const double *rowscale, int b, uint64_t nrec,
-                     uint64_t rows_out, double *out, hipStream_t stream, const double *init, bool short_lists, double avg_len)
+                     uint64_t rows_out, double *out, hipStream_t stream, const double *init, bool short_lists, double avg_len, unsigned block_limit)
 {
-   sparse_rows_sum_t<double>(ptr, idx, V, rowscale, b, nrec, rows_out, out, stream, init, short_lists, nullptr, avg_len);
+   sparse_rows_sum_t<double>(ptr, idx, V, rowscale, b, nrec, rows_out, out, stream, init, short_lists, nullptr, avg_len, block_limit);
 }
 void sparse_rows_sum_f32(const uint32_t *ptr, const uint32_t *idx, const float *V, const double *colw, int b, uint64_t nrec, uint64_t rows_out,
-                         double *out, hipStream_t stream, const double *init, bool short_lists, double avg_len)
+                         double *out, hipStream_t stream, const double *init, bool short_lists, double avg_len, unsigned block_limit)
 {
-   sparse_rows_sum_t<float>(ptr, idx, V, nullptr, b, nrec, rows_out, out, stream, init, short_lists, colw, avg_len);
+   sparse_rows_sum_t<float>(ptr, idx, V, nullptr, b, nrec, rows_out, out, stream, init, short_lists, colw, avg_len, block_limit);
 }
 
 // ------------------------------------------------------------------------------------------------

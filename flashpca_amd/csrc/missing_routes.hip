@@ -20,8 +20,12 @@ constexpr int I8W_B = 0, I8W_G = 640, I8W_M = 1280, I8W_D = 1920, I8W_ZERO = 256
               I8W_CSM = I8W_CSB + kern::I8_CS_STRIDE * kern::I8_SHARDS, I8W_TOTAL = I8W_CSM + kern::I8_CS_STRIDE * kern::I8_SHARDS;
 
 
-constexpr double CHEAP_SPARSE_BREAK_EVEN = 0.002; // ... and for passes on <= 4 slices (i8_mode)
+constexpr double CHEAP_SPARSE_BREAK_EVEN = 0.0035; // ... and for passes on <= 4 slices (i8_mode: measured)
 constexpr double SPARSE_BREAK_EVEN = 0.005; // missing-call rate at which the gathers cost what the E half of the GEMMs costs (= M2_CELL S / G_CALL at S = 7)
+// (measured again with today's gathers, profiles/gather_resident_ab.txt: the exact apply on route 3 | two-matrix kernels 0.5 % 14.8 | 17.6,
+//  0.6 % 16.1 | 17.5, 0.7 % 17.3 | 17.5 ms -- the lines now cross at 0.7 %.  SPARSE_BREAK_EVEN and G_CALL, which the hybrid route's
+//  per-SNP choice shares, are restated by tests/i8_planes_yardstick.py and test_missing_gathers_cpu.py and move together with them;
+//  until then 0.5-0.7 % takes the two-matrix kernels at up to 2.8 ms per apply more than the gathers would cost.)
 static void hybrid_classify(fpca_ctx *c);
 static void ensure_i8_alloc(fpca_ctx *c, int b);
 
@@ -332,8 +336,9 @@ int i8_mode(fpca_ctx *c, int b) // (classifies the SNPs the first time a rate ab
    if (sparse_ok && rate <= SPARSE_BREAK_EVEN) {
       // The eigensolver's cheap passes (fewer slices) cross over much earlier: the gathers cost the same whatever the slice count, the
       // indicator's half of a 4-slice two-matrix launch does not -- measured at 500,000 x 100,000, 16 columns, 4 slices
-      // (profiles/r06_cheap_route_breakeven.txt; apply in ms, gathers | two-matrix): 0.10 % 8.6 | 10.2, 0.15 % 9.3 | 10.2, 0.20 % 10.2 | 10.2,
-      // 0.30 % 11.8 | 10.2, 0.50 % 14.1 | 10.2.  Both routes read the same resident matrices (the lists stay for the exact passes), so
+      // (profiles/gather_resident_ab.txt; apply in ms, gathers | two-matrix): 0.10 % 7.17 | 10.1, 0.20 % 7.70 | 10.1, 0.30 % 8.50 | 10.1,
+      // 0.35 % 9.53 | 10.1, 0.40 % 10.12 | 10.1, 0.50 % 11.19 | 10.5 (r06_cheap_route_breakeven.txt, before the gathers read fp32 rows
+      // two columns a lane: 0.20 % 10.2 | 10.2).  Both routes read the same resident matrices (the lists stay for the exact passes), so
       // the choice is per pass.  (fpca_missing_mode reports the route of the exact passes.)
       if (c->i8_Sc > 0 && c->i8_Sc < c->i8_S && c->i8_Sc <= 4 && rate > CHEAP_SPARSE_BREAK_EVEN && !c->hyb_view) return I8M_FULL;
       return I8M_SPARSE;
@@ -349,6 +354,20 @@ bool sparse_on_side_stream(const fpca_ctx *c, int b)
 {
    static const double thr = FPCA_TEST_ENV("FPCA_SPARSE_SIDE_BYTES") ? atof(FPCA_TEST_ENV("FPCA_SPARSE_SIDE_BYTES")) : 2e9;
    return (double)(c->hyb_view ? c->hyb_sparse_nnz : c->n_missing) * b * 8.0 > thr;
+}
+
+// The grid of a side-stream gather: the blocks that are resident beside the workgroups of the GEMM it is released with (`gemm`:
+// kern::gemm_i8_footprint of that launch), so that a CU a GEMM workgroup leaves is not refilled with queued gather blocks before the
+// next one arrives -- while the gather still ends inside its GEMM.  A longer one has the chip to itself afterwards, where few blocks
+// are slow, and keeps the full grid (0: no limit).  Measured at 500,000 x 100,000, 16 columns (profiles/gather_resident_ab.txt; ms
+// per apply, resident | full grid): 7 slices 0.1 % 9.76 | 9.91, 0.2 % 10.31 | 11.02, 0.3 % 12.01 | 12.37, 0.4 % 14.76 | 13.54;
+// 4 slices 0.1 % 7.17 | 7.33, 0.2 % 7.70 | 8.06, 0.3 % 8.50 | 8.91.
+constexpr double RESIDENT_GATHER_MAX_RATE = 0.003; // listed calls per cell of the shard
+static unsigned side_gather_blocks(const fpca_ctx *c, const kern::CuFootprint &gemm, int b, bool f32, bool short_lists, double avg_len)
+{
+   const double listed = (double)(c->hyb_view ? c->hyb_sparse_nnz : c->n_missing);
+   if (listed > RESIDENT_GATHER_MAX_RATE * (double)c->N * (double)std::max<uint64_t>(c->P_g, 1)) return 0;
+   return kern::sparse_rows_sum_blocks_beside(gemm, b, f32, false, short_lists, avg_len);
 }
 
 // index lists of the missing calls, built once (by SNP from the SNP-major stream, by sample from the sample-major copy)
@@ -555,15 +574,17 @@ void xt_i8(fpca_ctx *c, const double *dB, int b, hipStream_t s, bool chain, hipE
                     c->hyb_n, I8M_NONE, nullptr, b, c->cur_S(), nullptr, s, nullptr, nullptr, true);
    if (mode == I8M_SPARSE || hyb) { // E'B: for every SNP the sum of the B rows of its missing samples, on the (low-priority) side
       hipStream_t gs = s;            // stream, released together with the GEMM
+      unsigned limit = 0;            // ... in a grid that is resident beside that GEMM's workgroups (an inline gather has the chip to itself)
       if (sparse_on_side_stream(c, b)) {
          HIP_CHECK(hipEventRecord(c->ev_aux_go, s));
          HIP_CHECK(hipStreamWaitEvent(c->aux_stream, c->ev_aux_go, 0));
          gs = c->aux_stream;
+         limit = side_gather_blocks(c, kern::gemm_i8_footprint(c->P_pad, c->cur_S(), b, false, I8M_NONE, false, c->d_packedK2 != nullptr), b, g32, false, 0.0);
       }
       if (g32)
-         kern::sparse_rows_sum_f32(c->d_snp_ptr, c->d_snp_idx, ob.copy32, ob.colw, b, c->P_g, c->P_pad, c->d_eplane, gs);
+         kern::sparse_rows_sum_f32(c->d_snp_ptr, c->d_snp_idx, ob.copy32, ob.colw, b, c->P_g, c->P_pad, c->d_eplane, gs, nullptr, false, 0, limit);
       else
-         kern::sparse_rows_sum(c->d_snp_ptr, c->d_snp_idx, dB, nullptr, b, c->P_g, c->P_pad, c->d_eplane, gs);
+         kern::sparse_rows_sum(c->d_snp_ptr, c->d_snp_idx, dB, nullptr, b, c->P_g, c->P_pad, c->d_eplane, gs, nullptr, false, 0, limit);
       if (hyb) kern::scatter_rows(c->d_hyb_plane, c->d_hyb_idx, c->hyb_n, b, c->d_eplane, gs); // (the gather wrote zeros there: empty lists)
       if (gs != s) {
          HIP_CHECK(hipEventRecord(c->ev_aux_done, c->aux_stream));
@@ -613,16 +634,20 @@ void x_i8(fpca_ctx *c, int b, double *dY, hipStream_t s, bool have_max, bool do_
       const double *init = hyb ? c->d_hyb_plane : nullptr;
       if (mode == I8M_SPARSE) { // E (mean T / sd): for every sample the sum of the scaled T rows of its missing SNPs
          hipStream_t gs = s;
+         unsigned limit = 0; // (as in xt_i8: a side-stream gather is resident beside the GEMM)
          const double per_sample = (double)(c->hyb_view ? c->hyb_sparse_nnz : c->n_missing) / (double)std::max<uint64_t>(c->N, 1); // listed calls per sample
          if (sparse_on_side_stream(c, b)) {
             HIP_CHECK(hipEventRecord(c->ev_aux_go, s)); // T is complete on s here (and the K2 combine has consumed the plane)
             HIP_CHECK(hipStreamWaitEvent(c->aux_stream, c->ev_aux_go, 0));
             gs = c->aux_stream;
+            // (the GEMM of this call's rows: with row chunks, the first chunk's, which is the one the gather starts beside)
+            const uint64_t rend = r1 ? r1 : c->N_pad, rows = rend > r0 ? rend - r0 : c->N_pad;
+            limit = side_gather_blocks(c, kern::gemm_i8_footprint(rows, c->cur_S(), b, false, I8M_NONE, false, c->i8_tiled), b, g32, true, per_sample);
          }
          if (g32)
-            kern::sparse_rows_sum_f32(c->d_smp_ptr, c->d_smp_idx, ot[1].copy32, ot[1].colw, b, c->N, c->N_pad, c->d_eplane, gs, init, true, per_sample);
+            kern::sparse_rows_sum_f32(c->d_smp_ptr, c->d_smp_idx, ot[1].copy32, ot[1].colw, b, c->N, c->N_pad, c->d_eplane, gs, init, true, per_sample, limit);
          else
-            kern::sparse_rows_sum(c->d_smp_ptr, c->d_smp_idx, ot[1].copy64, nullptr, b, c->N, c->N_pad, c->d_eplane, gs, init, true, per_sample);
+            kern::sparse_rows_sum(c->d_smp_ptr, c->d_smp_idx, ot[1].copy64, nullptr, b, c->N, c->N_pad, c->d_eplane, gs, init, true, per_sample, limit);
          if (gs != s) HIP_CHECK(hipEventRecord(c->ev_aux_done, c->aux_stream));
       }
    }

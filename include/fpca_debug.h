@@ -154,6 +154,15 @@ int fpca_debug_i8_slices(int route, int b, int S, uint64_t rows, uint64_t rows_p
  * `packed` (0 / 1) -- in the table's order; min(*count, cap) rows are written.  *count: the number of instances.  A test that launches
  * the GEMM under FPCA_I8_VERBOSE can rebuild the same six numbers from the plan and launch lines and hold its cases to the whole table. */
 int fpca_debug_i8_instances(int32_t *keys, int cap, int *count);
+/* diagnostic (tests/test_gather_blocks_cpu.py): the grid of a missing-call gather that runs on the side stream beside an int8 GEMM
+ * (csrc/missing_kernels.hip, gather_blocks_beside), host only, no device involved.  One workgroup of the GEMM: gemm_waves waves,
+ * gemm_vgprs registers per lane (as the compiler asks for them), gemm_lds bytes of LDS; gather_vgprs: registers per lane of the gather
+ * kernel (256-thread blocks, no LDS); ncu: compute units.  *limit: ncu times the blocks that stay resident on a CU beside the GEMM
+ * workgroups sharing it, at least ncu.  *grid_side / *grid_inline: the blocks of a launch of the one-wave-per-row kernels over rows_out
+ * rows on the side stream (under that limit) and inline (four rows a block, at most 65536 blocks).  FPCA_EINVAL unless gemm_waves is
+ * 1 .. 16, the register counts 1 .. 512, gemm_lds 0 .. 163840, ncu 1 .. 4096 and rows_out >= 1. */
+int fpca_debug_gather_blocks(int gemm_waves, int gemm_vgprs, int gemm_lds, int gather_vgprs, int ncu, uint64_t rows_out, uint32_t *limit,
+                             uint32_t *grid_side, uint32_t *grid_inline);
 
 /* diagnostic (tests): the F tail of fpca_ucca, from the host build of the same source the finishing kernel runs (no device
  * involved): F = r2 / (1 - r2) (n - k - 1) / k and P = upper tail of F(k, n - k - 1) at F = I_{1 - r2}((n - k - 1) / 2, k / 2).
