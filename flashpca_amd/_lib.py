@@ -135,6 +135,10 @@ SIGNATURES = {
     "fpca_king_related": (_I, [_P, _P, _D, C.c_uint32, _U64, _P, _P, _P, _P, C.POINTER(_U64)]),
     "fpca_king_cutoff_shared": (_I, [_P, _D, C.c_uint32, _P, C.POINTER(_U64)]),
     "fpca_king_classify": (_I, [_U64, _P, _P, _D, _P]),
+    "fpca_grm_block": (_I, [_P, _U64, _U64, _U64, _U64, _I, _P, _P]),
+    "fpca_grm_tri": (_I, [_P, _I, _P, _P]),
+    "fpca_grm_pairs": (_I, [_P, _P, _D, _I, _U64, _P, _P, _P, _P, C.POINTER(_U64)]),
+    "fpca_grm_cutoff": (_I, [_P, _D, _I, _P, C.POINTER(_U64)]),
     "fpca_snp_counts": (_I, [_P, _P, _P]),
     "fpca_sample_counts": (_I, [_P, _P, _P]),
     "fpca_hwe_exact": (_I, [_P, _P, _U64, _P]),
@@ -196,6 +200,7 @@ SIGNATURES = {
     "fpca_debug_king_rule": (_I, [_P, _P, _U64, _U64, _P, C.POINTER(_U64)]),
     "fpca_bench_king": (_I, [_P, _I, _P, C.POINTER(_D)]),
     "fpca_bench_king_rel": (_I, [_P, _I, _P, C.POINTER(_D)]),
+    "fpca_bench_grm": (_I, [_P, _I, _P, C.POINTER(_D)]),
     "fpca_debug_sample_qc_rule": (_I, [_P, _U64, _U64, _D, _P, C.POINTER(_U64)]),
     "fpca_debug_snp_qc_counts_rule": (_I, [_P, _P, _U64, _U64, _D, _D, _D, _P, C.POINTER(_U64)]),
     "fpca_bench_qc": (_I, [_P, _I, _P, C.POINTER(_D)]),

@@ -348,6 +348,67 @@ class Context:
         check(lib().fpca_bench_king_rel(self.h, int(reps), _p(ms), C.byref(macs)))
         return ms, macs.value
 
+    # ---- relationship matrix ------------------------------------------------------------------------
+    def grm_block(self, i0, ni, j0, nj, divisor="shared", counts=False):
+        """fpca_grm_block: the ni x nj array G of the genetic relationship matrix between sample i0 + a and sample j0 + b, any rectangle --
+        S_ij = sum over the SNPs of the products of the two samples' standardised genotypes (the context's own table; 0 at a missing
+        call), divided by n_ij, the live SNPs called in both (divisor "shared", GCTA's form; NaN when there is none), by the number of SNPs
+        ("p": the X X' / P of the PCA) or not at all ("none").  counts=True: (G, n) with n the ni x nj uint32 array of shared calls."""
+        i0, ni, j0, nj = int(i0), int(ni), int(j0), int(nj)
+        if min(i0, ni, j0, nj) < 0:
+            raise ValueError("i0, ni, j0 and nj are non-negative")
+        out = np.empty((max(ni, 1), max(nj, 1)), dtype=np.float64)  # (a zero-sized request still reaches the library's refusal)
+        n = np.empty(out.shape, dtype=np.uint32) if counts else None
+        check(lib().fpca_grm_block(self.h, i0, ni, j0, nj, _grm_divisor(divisor), _p(out), _p(n)))
+        return (out[:ni, :nj], n[:ni, :nj]) if counts else out[:ni, :nj]
+
+    def grm_tri(self, divisor="shared", counts=False):
+        """fpca_grm_tri: the lower triangle of the relationship matrix with its diagonal, row by row -- entry i (i + 1) / 2 + j is G_ij, j <= i
+        (GCTA's order), N (N + 1) / 2 doubles.  counts=True: (G, n) with the shared calls in the same order."""
+        size = self.N * (self.N + 1) // 2
+        out = np.empty(size, dtype=np.float64)
+        n = np.empty(size, dtype=np.uint32) if counts else None
+        check(lib().fpca_grm_tri(self.h, _grm_divisor(divisor), _p(out), _p(n)))
+        return (out, n) if counts else out
+
+    def grm_pairs(self, thr, keep=None, divisor="shared", max_pairs=1 << 24):
+        """fpca_grm_pairs: (i, j, g, shared) of every pair of samples i < j with relationship G > thr, sorted by (i, j), among the samples of
+        `keep` (a boolean array with one entry per sample; None: all).  FpcaError (code -4, the message names the count) when more than
+        max_pairs qualify."""
+        k8 = self._sample_keep(keep)
+        max_pairs = int(max_pairs)
+        if max_pairs < 0:
+            raise ValueError("max_pairs is non-negative")
+        room = max(min(max_pairs, self.N * (self.N - 1) // 2), 1)
+        i = np.empty(room, dtype=np.uint32)
+        j = np.empty(room, dtype=np.uint32)
+        g = np.empty(room, dtype=np.float64)
+        sh = np.empty(room, dtype=np.uint32)
+        n = C.c_uint64(0)
+        check(lib().fpca_grm_pairs(self.h, _p(k8), float(thr), _grm_divisor(divisor), max_pairs, _p(i), _p(j), _p(g), _p(sh), C.byref(n)))
+        return i[:n.value].copy(), j[:n.value].copy(), g[:n.value].copy(), sh[:n.value].copy()
+
+    def grm_cutoff(self, thr=0.025, keep=None, divisor="shared"):
+        """fpca_grm_cutoff: the boolean mask of the samples left after removing, among those of `keep` (None: all), one sample at a time
+        -- the one in most pairs with relationship above thr, the largest index among equals (king_cutoff's rule) -- until no such pair
+        remains.  The purpose of plink --rel-cutoff / gcta --grm-cutoff; 0.025 is the customary threshold."""
+        k8 = self._sample_keep(keep)
+        if k8 is None:
+            k8 = np.ones(self.N, dtype=np.uint8)
+        n = C.c_uint64(0)
+        check(lib().fpca_grm_cutoff(self.h, float(thr), _grm_divisor(divisor), _p(k8), C.byref(n)))
+        out = k8 != 0
+        assert int(out.sum()) == n.value
+        return out
+
+    def bench_grm(self, reps=5):
+        """fpca_bench_grm: (milliseconds of each of `reps` passes of the FP64 Gram kernel over the whole lower triangle, floating-point
+        operations one pass issues)."""
+        ms = np.zeros(int(reps), dtype=np.float64)
+        flops = C.c_double(0)
+        check(lib().fpca_bench_grm(self.h, int(reps), _p(ms), C.byref(flops)))
+        return ms, flops.value
+
     # ---- genotype census ------------------------------------------------------------------------------
     def snp_counts(self, samples=None):
         """fpca_snp_counts: the P x 4 uint32 array of genotype counts per SNP by raw .bed code (0 homozygous A1, 1 missing, 2 heterozygous,
@@ -1410,6 +1471,98 @@ def write_kin0(path, prefix, table):
                 raise ValueError("the table names sample %d; %s.fam has %d rows" % (max(i, j), prefix, len(ids)))
             f.write("%s\t%s\t%s\t%s\t%d\t%.17g\t%.17g\t%.17g\n" % (ids[i] + ids[j] + (n, float(hh) / n if n else float("nan"),
                                                                                 float(z) / n if n else float("nan"), float(phi))))
+
+
+GRM_DIVISOR = {"shared": 0, "p": 1, "none": 2}  # FPCA_GRM_DIV_*
+
+
+def _grm_divisor(divisor):
+    if isinstance(divisor, str):
+        if divisor not in GRM_DIVISOR:
+            raise ValueError("divisor must be one of %s" % sorted(GRM_DIVISOR))
+        return GRM_DIVISOR[divisor]
+    return int(divisor)  # (a number goes to the library as it is: its refusal names the three values)
+
+
+def _fam_ids(prefix):
+    ids = []
+    with open(prefix + ".fam") as f:
+        for line in f:
+            w = line.split()
+            if w:
+                ids.append((w[0], w[1]))
+    return ids
+
+
+def grm(prefix, divisor="shared", snps=None, maf=0.0, geno=1.0, ld=None, device=0):
+    """The genetic relationship matrix of a PLINK fileset (Context.grm_tri): a dict with `tri`, the packed lower triangle with the diagonal
+    (entry i (i + 1) / 2 + j, j <= i, over the rows of prefix.fam), `shared`, the SNPs called in both samples in the same order, and `ids`,
+    the (FID, IID) pairs -- what write_grm() takes.  Genotypes standardised as in flashpca() (binom2: the GRM of GCTA); snps / maf / geno /
+    ld as in king_cutoff(): applied first, over all samples, and the frequencies are those of the selected SNPs over all samples."""
+    qc = not (maf <= 0 and geno >= 1)
+    if ld is not None:
+        ld = _ld_args(ld)
+    N = count_fam_rows(prefix + ".fam")
+    with Context.from_bed(prefix + ".bed", N, device=device, accum="fp64") as full:
+        if snps is None and not qc and ld is None:
+            tri, shared = full.grm_tri(divisor, counts=True)
+        else:
+            with _select_snps(full, prefix, snps, qc, maf, geno, ld)[0] as sub:
+                tri, shared = sub.grm_tri(divisor, counts=True)
+    return dict(tri=tri, shared=shared, ids=_fam_ids(prefix))
+
+
+def rel_cutoff(prefix, thr=0.025, divisor="shared", snps=None, maf=0.0, geno=1.0, ld=None, keep=None, device=0):
+    """The unrelated samples of a PLINK fileset by the relationship matrix, in the manner of `plink --rel-cutoff thr` / `gcta --grm-cutoff
+    thr`: a boolean mask over the rows of prefix.fam in which no pair has G above thr (Context.grm_cutoff), to pass to flashpca(keep=).
+    snps / maf / geno / ld as in king_cutoff().  keep: a boolean array with one entry per sample; the cutoff runs among those (the
+    frequencies stay those of all samples).  Not byte-compatible with plink or gcta (the order in which samples go differs)."""
+    qc = not (maf <= 0 and geno >= 1)
+    if ld is not None:
+        ld = _ld_args(ld)
+    N = count_fam_rows(prefix + ".fam")
+    with Context.from_bed(prefix + ".bed", N, device=device, accum="fp64") as full:
+        if snps is None and not qc and ld is None:
+            return full.grm_cutoff(thr, keep=keep, divisor=divisor)
+        with _select_snps(full, prefix, snps, qc, maf, geno, ld)[0] as sub:
+            return sub.grm_cutoff(thr, keep=keep, divisor=divisor)
+
+
+def write_grm(path, ids, tri, shared):
+    """Write a relationship matrix in GCTA's binary format: path.grm.bin (float32, the packed lower triangle with the diagonal, row by
+    row), path.grm.N.bin (float32, the shared-SNP counts in the same order) and path.grm.id (one `FID<tab>IID` line per sample).  ids:
+    (FID, IID) pairs; tri and shared: N (N + 1) / 2 entries each, as grm() returns them."""
+    ids = [tuple(x) for x in ids]
+    n = len(ids)
+    tri = np.asarray(tri)
+    shared = np.asarray(shared)
+    if tri.shape != (n * (n + 1) // 2,) or shared.shape != tri.shape:
+        raise ValueError("%d samples have a triangle of %d entries; tri and shared have shapes %s and %s"
+                         % (n, n * (n + 1) // 2, tri.shape, shared.shape))
+    if any(len(x) != 2 for x in ids):
+        raise ValueError("ids holds one (FID, IID) pair per sample")
+    tri.astype("<f4").tofile(path + ".grm.bin")
+    shared.astype("<f4").tofile(path + ".grm.N.bin")
+    with open(path + ".grm.id", "w") as f:
+        for fid, iid in ids:
+            f.write("%s\t%s\n" % (fid, iid))
+
+
+def read_grm(path):
+    """Read path.grm.bin / .grm.N.bin / .grm.id (GCTA's binary format) back: a dict `tri` (float32), `shared` (float32), `ids`."""
+    ids = []
+    with open(path + ".grm.id") as f:
+        for line in f:
+            w = line.rstrip("\n").split("\t") if "\t" in line else line.split()
+            if w and w != [""]:
+                ids.append((w[0], w[1]))
+    n = len(ids)
+    tri = np.fromfile(path + ".grm.bin", dtype="<f4")
+    shared = np.fromfile(path + ".grm.N.bin", dtype="<f4")
+    if tri.shape != (n * (n + 1) // 2,) or shared.shape != tri.shape:
+        raise ValueError("%s.grm.id names %d samples: a triangle of %d entries; .grm.bin holds %d and .grm.N.bin %d"
+                         % (path, n, n * (n + 1) // 2, tri.size, shared.size))
+    return dict(tri=tri, shared=shared, ids=ids)
 
 
 def project(X, loadings, orig_mean=None, orig_sd=None, ref_alleles=None, divisor="p", device=0, check_bim=True):

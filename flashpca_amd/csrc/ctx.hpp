@@ -27,6 +27,10 @@
 //   king_rel.hip        fpca_king_counts_block / fpca_king_related / fpca_king_cutoff_shared / fpca_king_classify: the relationship table --
 //                       shared calls, IBS0, het-het beside phi (k_king_rel, seven products per pair, a loop of its own), a minimum-shared
 //                       filter in front of king.hip's host rule, the degree / parent-offspring classification on the host
+//   grm.hip             fpca_grm_block / fpca_grm_tri / fpca_grm_pairs / fpca_grm_cutoff: the relationship matrix X X' / n of the standardised
+//                       genotypes on the same sample-major copy -- the sums on the FP64 MFMA with the per-SNP table staged in LDS (k_grm_dot),
+//                       the shared-call counts as one int8 product (k_grm_shared), the divide and the three outputs (k_grm_finish), in slabs
+//                       of rows; king.hip's host rule for the cutoff
 //   qc_census.hip       fpca_snp_counts / fpca_sample_counts / fpca_hwe_exact / fpca_sample_qc / fpca_snp_qc_samples: genotype counts per SNP
 //                       over chosen samples (k_snp_counts) and per sample over chosen SNPs (k_sample_counts, a column census with vertical
 //                       counters), the HWE exact test (k_hwe_exact, one SNP per lane), the --mind and --geno / --maf / --hwe rules on the host

@@ -291,6 +291,48 @@ int fpca_king_related(fpca_ctx *ctx, const uint8_t *keep /* [N] or NULL */, doub
 int fpca_king_cutoff_shared(fpca_ctx *ctx, double thr, uint32_t min_shared, uint8_t *keep /* [N] in/out */, uint64_t *n_kept);
 int fpca_king_classify(uint64_t n_pairs, const double *phi, const uint32_t *counts /* [n_pairs][6] */, double po_ibs0, uint8_t *type /* [n_pairs] */);
 
+/* Relationship matrix: the genetic relationship matrix (GRM) of the samples of the resident matrix -- the X X' / P whose eigenvectors
+ * fpca_pca computes without forming it -- on the FP64 matrix cores, and a relatedness cutoff on top of it (the purpose of plink
+ * --rel-cutoff / gcta --grm-cutoff).  The mask it leaves feeds fpca_set_sample_mask.
+ *   For SNP s of the context, t_s[code] is the context's table entry: (x - mean_s) / sd_s at a call, 0 at a missing call, all four entries 0
+ *   when sd_s <= 1e-9 or NaN.  mean_s and sd_s are the context's own: over all N samples under the context's standardisation, or what
+ *   fpca_set_meansd loaded (with FPCA_STANDARDISE_BINOM2 this is the GRM of Yang et al. / GCTA; no frequency is re-estimated here).  A SNP
+ *   is LIVE when its table is not all zero.
+ *      z_is = t_s[code_is]        S_ij = sum_s z_is z_js        n_ij = the live SNPs called in both i and j
+ *   SNPs that are not live contribute to neither sum.  G_ij is
+ *      S_ij / n_ij   under FPCA_GRM_DIV_SHARED (the pairwise-complete form of GCTA)
+ *      S_ij / P_g    under FPCA_GRM_DIV_P      (X X' / P of fpca_pca under FPCA_DIVISOR_P: missing calls mean-imputed)
+ *      S_ij          under FPCA_GRM_DIV_NONE
+ *   each ONE fp64 divide of S_ij by the integer converted to double.  Under FPCA_GRM_DIV_SHARED, n_ij == 0 is tested and gives NaN.  A NaN is
+ *   never above a threshold; all comparisons are strict (G > thr).  S_ij is accumulated in fp64 without atomics and without a split along
+ *   the SNPs: a call is deterministic, and G_ij and G_ji are the same bits.
+ *   fpca_grm_block   grm[ni][nj], row-major: grm[a][b] is G of samples i0 + a and j0 + b, for any rectangle (j <= i included); shared
+ *                    (may be NULL): n likewise.  FPCA_EINVAL when grm would exceed 1 GiB.
+ *   fpca_grm_tri     the lower triangle with the diagonal, row by row: entry i (i + 1) / 2 + j is G_ij, j <= i (GCTA's order), N (N + 1) / 2
+ *                    entries; shared (may be NULL): n in the same order.  Host buffers of any size; computed in slabs of rows, each
+ *                    downloaded as it finishes.
+ *   fpca_grm_pairs   every pair i < j with G > thr whose samples both have keep != 0 (keep: N bytes, or NULL for all), sorted by (i, j), in
+ *                    i[], j[], g[] and (may be NULL) shared[] (max_pairs entries each); *n_pairs = their number.  When more than max_pairs
+ *                    qualify the call returns FPCA_ENOMEM, *n_pairs is the number needed and the message names it; the arrays are then not
+ *                    written.
+ *   fpca_grm_cutoff  keep[N] in and out, as for fpca_king_cutoff: the pair pass above (room for 2^26 pairs, else FPCA_ENOMEM), then
+ *                    fpca_king_cutoff's rule on the host, unchanged.  0.025 is the customary threshold.  Byte parity with plink or gcta is
+ *                    not claimed.
+ *   Every call makes its own sample-major copy of the packed matrix and a scratch of at most 256 MiB for the sums and counts of a slab
+ *   (FPCA_ENOMEM with both sizes in the message when one does not fit) and frees them before it returns.
+ *   All: FPCA_EINVAL, before any device work, for a NULL argument, a divisor other than the three, a range outside the context or a
+ *   zero-sized block, a NaN thr, a dense context, a context under a sample mask, one shard of several, more than 2^28 SNPs (n_ij fits 32
+ *   bits) and 2^32 samples or more.  The context is not changed. */
+#define FPCA_GRM_DIV_SHARED 0
+#define FPCA_GRM_DIV_P 1
+#define FPCA_GRM_DIV_NONE 2
+int fpca_grm_block(fpca_ctx *ctx, uint64_t i0, uint64_t ni, uint64_t j0, uint64_t nj, int divisor, double *grm /* [ni][nj] */,
+                   uint32_t *shared /* [ni][nj] or NULL */);
+int fpca_grm_tri(fpca_ctx *ctx, int divisor, double *grm /* [N (N + 1) / 2] */, uint32_t *shared /* same, or NULL */);
+int fpca_grm_pairs(fpca_ctx *ctx, const uint8_t *keep /* [N] or NULL */, double thr, int divisor, uint64_t max_pairs, uint32_t *i, uint32_t *j,
+                   double *g, uint32_t *shared /* or NULL */, uint64_t *n_pairs);
+int fpca_grm_cutoff(fpca_ctx *ctx, double thr, int divisor, uint8_t *keep /* [N] in/out */, uint64_t *n_kept);
+
 /* Genotype census: counts per SNP over a chosen set of samples, counts per sample over a chosen set of SNPs, the Hardy-Weinberg exact test
  * on such counts, and the two QC rules on top of them -- PLINK's --mind (per-sample call rate) and --geno / --maf / --hwe over the KEPT
  * samples.  The masks they leave feed fpca_set_sample_mask and fpca_create_snp_subset.

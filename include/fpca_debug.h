@@ -211,6 +211,12 @@ int fpca_bench_king(fpca_ctx *ctx, int reps, double *ms, double *macs);
 /* the same for the pair kernel of fpca_king_related (scripts/king_rel_measure.py), at thr = 0.0884, min_shared = 0, no keep: seven
  * products per pair of 32-sample blocks on the general path, two where neither block has a missing call. */
 int fpca_bench_king_rel(fpca_ctx *ctx, int reps, double *ms, double *macs);
+/* time the FP64 Gram kernel of the relationship matrix alone (k_grm_dot, scripts/grm_measure.py) over the whole lower triangle, slab by slab as
+ * fpca_grm_tri launches it: the sample-major copy, the totals and the slab scratch are ready before the clock starts; one untimed pass,
+ * then `reps` passes with a pair of HIP events around each, ms[reps].  *flops (may be NULL): floating-point operations one pass issues
+ * (2 x 32 x 32 x 4 pitch per 32 x 32 block of pairs on or below the diagonal, pad SNPs included).  Test build with FPCA_GRM_BENCH_SHARED=1:
+ * the shared-call count kernel (k_grm_shared) is timed instead. */
+int fpca_bench_grm(fpca_ctx *ctx, int reps, double *ms, double *flops);
 /* diagnostic (tests): the rules of fpca_sample_qc / fpca_snp_qc_samples on caller arrays, no context and no device involved.  counts:
  * uint32 [N][4] / [P][4] by raw code; n_snps: the SNPs the per-sample counts were taken over; n: the samples the per-SNP counts were taken
  * over; p_hwe[P]: the p-values, read only when min_hwe_p > 0 (may be NULL otherwise); samples[N] / keep[P] in and out.  FPCA_EINVAL for
