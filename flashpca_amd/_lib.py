@@ -175,6 +175,7 @@ SIGNATURES = {
     "fpca_bench_stats": (_I, [_P, _I, C.POINTER(_D), C.POINTER(_D)]),
     "fpca_debug_mfma_probe": (_I, [_P, _P, _P]),
     "fpca_debug_mfma_i8_probe": (_I, [_P, _P, _P]),
+    "fpca_debug_mfma_i8_ports": (_I, [_I, _I, _P, _P, _P]),
     "fpca_debug_mfma_peak": (_I, [_I, _I, _I, C.POINTER(_D)]),
     "fpca_debug_k4": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _P, _P]),
     "fpca_debug_k4_bench": (_I, [_P, _I, _I, _I, C.POINTER(_D), C.POINTER(_D)]),

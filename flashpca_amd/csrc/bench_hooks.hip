@@ -188,6 +188,22 @@ int fpca_debug_mfma_i8_probe(const int8_t *A, const int8_t *Bt, int32_t *D)
    });
 }
 
+int fpca_debug_mfma_i8_ports(int shape, int exchanged, const int8_t *A, const int8_t *Bt, int32_t *D)
+{
+   return guarded([&] {
+      static const char *FN = "fpca_debug_mfma_i8_ports";
+      if ((shape != 32 && shape != 16) || !A || !Bt || !D) throw Error(FPCA_EINVAL, "bad argument to fpca_debug_mfma_i8_ports");
+      const size_t nd = (size_t)shape * shape;
+      DevMem<int8_t> dA(1024, FN, "A"), dB(1024, FN, "Bt");
+      DevMem<int> dD(nd, FN, "D");
+      HIP_CHECK(hipMemcpy(dA.p, A, 1024, hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(dB.p, Bt, 1024, hipMemcpyHostToDevice));
+      kern::mfma_i8_ports(shape, exchanged != 0, dA.p, dB.p, dD.p, nullptr);
+      HIP_CHECK(hipDeviceSynchronize());
+      HIP_CHECK(hipMemcpy(D, dD.p, nd * sizeof(int), hipMemcpyDeviceToHost));
+   });
+}
+
 // The K4 hooks start by filling the context's split-K partial buffer (at the size earlier calls left it) with NaNs (all bits set): a
 // partial plane that a kernel fails to write then shows in the result instead of reading as a zero of fresh memory -- from the
 // second call of a kind on a context on, once the buffer has its size.
@@ -654,11 +670,31 @@ int fpca_debug_scratch_fail_at(uint64_t n)
 int fpca_debug_mfma_peak(int waves_per_simd, int iters, int pattern, double *tflops)
 {
    return guarded([&] {
-      if (waves_per_simd < 1 || waves_per_simd > 8 || iters < 10 || pattern < 0 || (pattern > 3 && pattern != 10 && pattern != 11) || !tflops)
+      if (waves_per_simd < 1 || waves_per_simd > 8 || iters < 10 || pattern < 0 || (pattern > 3 && pattern < 10) || pattern > 17 || !tflops)
          throw Error(FPCA_EINVAL, "bad argument");
-      if (pattern >= 10) // v_mfma_i32_32x32x32_i8 (TOP/s): 10 = zero operands, 11 = random operands
-         *tflops = kern::mfma_i8_peak_tops(waves_per_simd, iters, pattern == 11 ? 0x1234567u : 0u, nullptr);
-      else
+      if (pattern >= 10) {
+         // v_mfma_i32_32x32x32_i8 (TOP/s): 10 = zero operands, 11 = random operands (the same bytes on both ports and in both sets).
+         // Which port pays for the bytes:  12 = A random, B zero;  13 = A zero, B random  (equal sets: nothing changes between
+         // instructions);  14 = A genotype bytes, B random;  15 = A random, B genotype bytes  (the two sets of a port seeded
+         // differently, A alternating every instruction, B holding one set for two).  What the order costs:  16 = as 14 with A holding
+         // and B alternating, the order of k_gemm_i8's main loop;  17 = B holding one set for two: the stream of 14 under its own number
+         using kern::I8_FILL_GENO;
+         using kern::I8_FILL_RANDOM;
+         using kern::I8_FILL_ZERO;
+         const uint32_t s0 = 0x1234567u;
+         kern::I8PeakFill f{{s0, s0, s0, s0}, {I8_FILL_ZERO, I8_FILL_ZERO, I8_FILL_ZERO, I8_FILL_ZERO}, 0};
+         const auto port = [&](int p, uint32_t kind) { f.kind[2 * p] = f.kind[2 * p + 1] = kind; };
+         if (pattern == 11) port(0, I8_FILL_RANDOM), port(1, I8_FILL_RANDOM);
+         if (pattern == 12) port(0, I8_FILL_RANDOM);
+         if (pattern == 13) port(1, I8_FILL_RANDOM);
+         if (pattern >= 14) {
+            port(0, pattern == 15 ? I8_FILL_RANDOM : I8_FILL_GENO);
+            port(1, pattern == 15 ? I8_FILL_GENO : I8_FILL_RANDOM);
+            f.seed[1] = 0x2468ace1u, f.seed[2] = 0x9abcdef3u, f.seed[3] = 0x5f3759dfu;
+            f.order = pattern == 16 ? 1 : 0;
+         }
+         *tflops = kern::mfma_i8_peak_tops(waves_per_simd, iters, f, nullptr);
+      } else
          *tflops = kern::mfma_peak_tflops(waves_per_simd, iters, pattern, nullptr);
    });
 }

@@ -175,8 +175,16 @@ void transpose_packed(const uint8_t *in, size_t pitch_in, uint64_t N_pad, uint64
                       hipStream_t stream, bool tiled = false /* write the band-tiled layout */);
 // out = the band-tiled arrangement of the row-major records in[rows][pitch] (rows a multiple of 32, pitch of 64)
 void tile_packed(const uint8_t *in, size_t pitch, uint64_t rows, uint8_t *out, hipStream_t stream);
-double mfma_i8_peak_tops(int waves_per_simd, int iters, uint32_t fill, hipStream_t stream);
+// what the bare int8 MFMA stream multiplies: two register sets per operand port, index 0, 1 = the sets of source A, 2, 3 = of source B
+enum { I8_FILL_ZERO = 0, I8_FILL_RANDOM = 1 /* hashed bytes */, I8_FILL_GENO = 2 /* bytes 0, 1, 2, a third each */ };
+struct I8PeakFill {
+   uint32_t seed[4]; // hash seed of each set (equal seeds and kinds: equal sets, nothing changes between instructions)
+   uint32_t kind[4]; // I8_FILL_*
+   int order;        // 0: A alternates its sets every instruction, B holds one for two; 1: A holds, B alternates
+};
+double mfma_i8_peak_tops(int waves_per_simd, int iters, const I8PeakFill &fill, hipStream_t stream);
 void mfma_i8_probe(const int8_t *A, const int8_t *Bt, int *D, hipStream_t stream);
+void mfma_i8_ports(int shape /* 32 | 16 */, bool exchanged, const int8_t *A, const int8_t *Bt, int *D, hipStream_t stream);
 
 // ---- missing calls of the exact-integer path: index lists, gather-sums, row shuffles (missing_kernels.hip) ----
 // the hybrid missing-indicator route's row shuffles

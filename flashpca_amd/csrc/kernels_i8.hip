@@ -625,8 +625,12 @@ template <int MODE>
 __device__ __forceinline__ bool i8_decode(uint32_t w, v4i &ag, v4i &am, uint32_t tab1)
 {
    // byte[code] of the two integer matrices: G.M (dosage, 0 if missing) and E = 1 - M (missing indicator): code 0 -> (2,0),
-   // 1 (missing) -> (0,1), 2 -> (1,0), 3 -> (0,0).  E instead of M because E is almost all zeros: the products vanish and
-   // the power-limited matrix pipe clocks higher; M'Q is recovered exactly in the combine as 1'Q - E'Q.
+   // 1 (missing) -> (0,1), 2 -> (1,0), 3 -> (0,0).  E instead of M because E is almost all zeros; M'Q is recovered exactly in the
+   // combine as 1'Q - E'Q.  What zeros and small bytes are worth depends on the PORT they enter the MFMA by (the bare stream,
+   // profiles/mfma_ports_ab.txt section A, 2 waves per SIMD, TOP/s): random bytes on both ports 3340, zeros on both 4650; zeros on one
+   // port alone already give 4420-4570 (zero A, random B) and 4600-4960 (random A, zero B); genotype bytes {0, 1, 2} against random
+   // digits 3680-3710 with the genotypes on source A and 4310-4340 with them on source B.  So the fragments decoded here are the
+   // SECOND operand of every MFMA of k_gemm_i8 and the slice-columns the first.
    // (the one-matrix kernel takes its table as an argument: G.M for the genotype products, E for the missing-indicator
    //  products of the SNPs whose missing calls are too many for the sparse route -- gemm_i8 `e_only`)
    const uint32_t tabG = MODE == I8_NO_MISSING ? tab1 : 0x00010002u, tabM = 0x00000100u;
@@ -711,7 +715,8 @@ __global__ __launch_bounds__(C::THREADS, 1) void k_gemm_i8(const uint8_t *__rest
    uint32_t pvoff[MT];
 #pragma unroll
    for (int m = 0; m < MT; m++)
-      pvoff[m] = C::TILED ? (uint32_t)((wr * MT + m) * 32 * pitch + lane * 16) // band of the m-tile, piece (kh, li) of a 1 KB half block
+      pvoff[m] = C::TILED ? (uint32_t)(wr * MT * 32 * pitch + lane * 16) // band of the wave's first m-tile, piece (kh, li) of a 1 KB half block: the
+                                                                           // band of m-tile m lies 32 m pitch further, on the scalar base (issue_p)
                           : (uint32_t)((wr * 32 * MT + 32 * m + li) * pitch + kh * (KC / 8));
    const uint8_t *prow = packed + row0 * pitch;
    const uint32_t aQ0 = lds_base + (uint32_t)(wc * 32 * NT + li) * LDQ + kh * (KC / 2);
@@ -737,8 +742,9 @@ __global__ __launch_bounds__(C::THREADS, 1) void k_gemm_i8(const uint8_t *__rest
       const uint8_t *pb = prow + (size_t)cc * (C::TILED ? 2048 : KC / 4);
 #pragma unroll
       for (int m = 0; m < MT; m++) {
-         dst[m][0] = gload16<0, C::NT_P>(pb, pvoff[m]);
-         if constexpr (PW == 2) dst[m][1] = gload16<(C::TILED ? 1024 : 16), C::NT_P>(pb, pvoff[m]);
+         const uint8_t *pbm = C::TILED ? pb + (size_t)(32 * m) * pitch : pb;
+         dst[m][0] = gload16<0, C::NT_P>(pbm, pvoff[C::TILED ? 0 : m]);
+         if constexpr (PW == 2) dst[m][1] = gload16<(C::TILED ? 1024 : 16), C::NT_P>(pbm, pvoff[C::TILED ? 0 : m]);
       }
    };
    auto store_q = [&](auto rr, unsigned char *st, auto behind) { // `behind`: loads issued after the NP pieces (the packed words, or none)
@@ -914,9 +920,9 @@ __global__ __launch_bounds__(C::THREADS, 1) void k_gemm_i8(const uint8_t *__rest
          static_for<NG>([&](auto jj) {
             constexpr int j = decltype(jj)::value, n = g * NG + j;
             if constexpr (n < NTF) {
-               acc[0][m][n] = __builtin_amdgcn_mfma_i32_32x32x32_i8(ag[akey & AMASK], bq[bkey & 1][0][j], acc[0][m][n], 0, 0, 0);
+               acc[0][m][n] = __builtin_amdgcn_mfma_i32_32x32x32_i8(bq[bkey & 1][0][j], ag[akey & AMASK], acc[0][m][n], 0, 0, 0);
                if constexpr (MODE == I8_FULL)
-                  acc[1][m][n] = __builtin_amdgcn_mfma_i32_32x32x32_i8(am[akey & AMASK], bq[bkey & 1][NQ - 1][j], acc[1][m][n], 0, 0, 0);
+                  acc[1][m][n] = __builtin_amdgcn_mfma_i32_32x32x32_i8(bq[bkey & 1][NQ - 1][j], am[akey & AMASK], acc[1][m][n], 0, 0, 0);
             }
             if constexpr (j == 0 && akey1 != akey)
                enz[akey1 & AMASK] = i8_decode<MODE>(pk[m1][ks1 >> 2][ks1 & 3], ag[akey1 & AMASK], am[akey1 & AMASK], tab1);
@@ -933,8 +939,8 @@ __global__ __launch_bounds__(C::THREADS, 1) void k_gemm_i8(const uint8_t *__rest
                t0[q] = (int)r[0];
                t1[q] = (int)r[1];
             }
-            acch[0][m][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(t0, bqh, acch[0][m][0], 0, 0, 0);
-            acch[0][m][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(t1, bqh, acch[0][m][1], 0, 0, 0);
+            acch[0][m][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(bqh, t0, acch[0][m][0], 0, 0, 0);
+            acch[0][m][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(bqh, t1, acch[0][m][1], 0, 0, 0);
             if constexpr (MATS == 2) { // the missing-indicator matrix against its own operand (K3) or the same one (K2)
                v4i u0 = am[m], u1 = am[2 + m];
 #pragma unroll
@@ -943,8 +949,8 @@ __global__ __launch_bounds__(C::THREADS, 1) void k_gemm_i8(const uint8_t *__rest
                   u0[q] = (int)r[0];
                   u1[q] = (int)r[1];
                }
-               acch[1][m][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(u0, TWO ? bqh2 : bqh, acch[1][m][0], 0, 0, 0);
-               acch[1][m][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(u1, TWO ? bqh2 : bqh, acch[1][m][1], 0, 0, 0);
+               acch[1][m][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(TWO ? bqh2 : bqh, u0, acch[1][m][0], 0, 0, 0);
+               acch[1][m][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(TWO ? bqh2 : bqh, u1, acch[1][m][1], 0, 0, 0);
             }
          }
          if constexpr (MODE == I8_SKIP_EMPTY) {
@@ -952,7 +958,7 @@ __global__ __launch_bounds__(C::THREADS, 1) void k_gemm_i8(const uint8_t *__rest
                static_for<NG>([&](auto jj) {
                   constexpr int j = decltype(jj)::value, n = g * NG + j;
                   if constexpr (n < NT)
-                     acc[1][m][n] = __builtin_amdgcn_mfma_i32_32x32x32_i8(am[akey & AMASK], bq[bkey & 1][NQ - 1][j], acc[1][m][n], 0, 0, 0);
+                     acc[1][m][n] = __builtin_amdgcn_mfma_i32_32x32x32_i8(bq[bkey & 1][NQ - 1][j], am[akey & AMASK], acc[1][m][n], 0, 0, 0);
                });
             }
          }
@@ -995,15 +1001,21 @@ __global__ __launch_bounds__(C::THREADS, 1) void k_gemm_i8(const uint8_t *__rest
    double *out = (split == 0 ? part + (((size_t)zblk * rows_pad + row0 + wr * 32 * MT) * 2) * bw
                              : part + (size_t)zb * rows_pad * 2 * bw +
                                   ((((size_t)(split - 1) * zb + zblk) * rowsB + (row0 - rowB0) + wr * 32 * MT) * 2) * bw) +
-                 li;
+                 (size_t)li * 2 * bw + 16 * kh; // lane (li, kh): row li of the m-tile, columns 16 kh .. of the 32-column tile
    //
    // Register discipline: the 256 accumulators own every AGPR, and reading ONE element of an AGPR-resident 16-vector makes
    // the compiler copy the whole vector to VGPRs, so any epilogue that walks rows across tiles keeps hundreds of extra
    // VGPRs alive and the allocator answers by spilling INSIDE the main loop (measured: 10 scratch stores per chunk,
    // 3.5 GB of spill traffic per launch, matrix pipe 48 % busy).  So the tiles are dumped to LDS one at a time (the operand
    // tiles are dead by now; 4 KB per tile and wave) and the recombination runs from LDS with a handful of registers.
+   //
+   // The slice-columns are the MFMAs' FIRST operand and the genotype rows their second (source B is the port whose bytes cost the
+   // power -- DESIGN.md 3a, "Which port carries the digits"), so an accumulator tile is the TRANSPOSE of the tile of partials:
+   // register r of lane (li, kh) is column (r & 3) + 8 (r >> 2) + 4 kh of genotype row li.  The dump keeps the addresses it had
+   // with the operands the other way round (conflict-free), so the tile lies in LDS as [column][row]; a lane recombines half a
+   // row of partials and writes it as one whole 128-byte line, 16 bytes at a time: L2 puts the line together.
    __syncthreads(); // every wave has finished reading the operand tiles
-   constexpr int WREG = NT * 4096; // bytes of a wave's private tile area: [NT][32 rows][32 cols] int32
+   constexpr int WREG = NT * 4096; // bytes of a wave's private tile area: [NT][32 cols][32 rows] int32
    double *sW = reinterpret_cast<double *>(smem + C::WAVES * WREG); // weights of this workgroup's slice-columns: [2][COLS]
    constexpr int WCOLS = C::WC * NT * 32; // (HALF: the 16 columns missing from the last tile carry zero weights)
    for (int t = tid; t < WCOLS; t += C::THREADS) {
@@ -1014,8 +1026,8 @@ __global__ __launch_bounds__(C::THREADS, 1) void k_gemm_i8(const uint8_t *__rest
    static_assert(C::LDS_BYTES >= C::WAVES * WREG + 2 * WCOLS * 8, "epilogue LDS layout");
    if (idle) return; // (behind the last barrier)
    int *sT = reinterpret_cast<int *>(smem + wave * WREG);
-   const double *sWl = sW + wc * 32 * NT + li;
-   const int kb = bw / 32; // a lane's tiles n, n + kb, ... feed the same virtual column 32 ((tile0 + n) % kb) + li
+   const double *sWl = sW + wc * 32 * NT + 16 * kh;
+   const int kb = bw / 32; // tiles n, n + kb, ... feed the same 32 virtual columns, 32 ((tile0 + n) % kb) ..
 #pragma unroll
    for (int a = 0; a < MATS; a++) // (the E plane of the partials is not written in I8_NO_MISSING mode: the combine knows)
 #pragma unroll
@@ -1027,26 +1039,28 @@ __global__ __launch_bounds__(C::THREADS, 1) void k_gemm_i8(const uint8_t *__rest
             for (int r = 0; r < 16; r++) sT[(n * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh) * 32 + li] = v[r];
             __builtin_amdgcn_sched_barrier(0);
          }
-         if constexpr (HALF) { // 16x16 C/D map: register r of lane l = D[4 (l >> 4) + r][l & 15]; columns 16..31 of the tile are zero
+         if constexpr (HALF) { // 16x16 C/D map: register r of lane l = column 4 (l >> 4) + r of row l & 15 of row half t; columns 16..31 of the tile are zero
 #pragma unroll
             for (int t = 0; t < 2; t++)
 #pragma unroll
                for (int r = 0; r < 4; r++) {
-                  const int row = 16 * t + 4 * (lane >> 4) + r;
-                  sT[(NTF * 32 + row) * 32 + (lane & 15)] = acch[a][m][t][r];
-                  sT[(NTF * 32 + row) * 32 + 16 + (lane & 15)] = 0;
+                  const int col = 4 * (lane >> 4) + r;
+                  sT[(NTF * 32 + col) * 32 + 16 * t + (lane & 15)] = acch[a][m][t][r];
+                  sT[(NTF * 32 + 16 + col) * 32 + 16 * t + (lane & 15)] = 0;
                }
          }
          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
          __builtin_amdgcn_wave_barrier();
-         // lane (li, kh) recombines rows 16 kh .. 16 kh + 15 of column li
-         for (int j = 0; j < 16; j++) {
-            const int row = 16 * kh + j;
+         // lane (li, kh) recombines columns 16 kh .. 16 kh + 15 of row li, two at a time (the weight goes by the column)
+         for (int j = 0; j < 16; j += 2) {
+            const int col = 16 * kh + j;
             for (int k = 0; k < kb; k++) {
-               double acc64 = 0.0;
-               for (int n = NT - 1 - ((NT - 1 - k) % kb); n >= 0; n -= kb) // tiles n == k (mod kb), last slice first
-                  acc64 += sWl[a * WCOLS + 32 * n] * (double)sT[(n * 32 + row) * 32 + li];
-               out[((size_t)(32 * m + row) * 2 + a) * bw + 32 * ((tile0 + k) % kb)] = acc64;
+               double acc0 = 0.0, acc1 = 0.0;
+               for (int n = NT - 1 - ((NT - 1 - k) % kb); n >= 0; n -= kb) { // tiles n == k (mod kb), last slice first
+                  acc0 += sWl[a * WCOLS + 32 * n + j] * (double)sT[(n * 32 + col) * 32 + li];
+                  acc1 += sWl[a * WCOLS + 32 * n + j + 1] * (double)sT[(n * 32 + col + 1) * 32 + li];
+               }
+               *reinterpret_cast<double2 *>(&out[((size_t)(32 * m) * 2 + a) * bw + 32 * ((tile0 + k) % kb) + j]) = make_double2(acc0, acc1);
             }
          }
          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -1628,14 +1642,63 @@ void mfma_i8_probe(const int8_t *A, const int8_t *Bt, int *D, hipStream_t stream
    launch_check();
 }
 
+// diagnostic: the two int8 instructions of k_gemm_i8 with their operands in the given order or EXCHANGED, stored through the register
+// map of the given order -- exchanged, the same registers hold the transposed tile.
+//   shape 32: v_mfma_i32_32x32x32_i8, A[32][32], Bt[32][32], D[32][32]      (k_mfma_i8_probe's layout)
+//   shape 16: v_mfma_i32_16x16x64_i8, A[16][64], Bt[16][64], D[16][16]: lane l supplies bytes 16 (l >> 4) .. of row / column l & 15;
+//             register r of lane l = D[4 (l >> 4) + r][l & 15]
+__global__ void k_mfma_i8_ports(int shape, int exchanged, const int8_t *A, const int8_t *Bt, int *D)
+{
+   const int lane = threadIdx.x & 63;
+   if (shape == 32) {
+      const int li = lane & 31, kh = lane >> 5;
+      const v4i a = *reinterpret_cast<const v4i *>(A + li * 32 + kh * 16), b = *reinterpret_cast<const v4i *>(Bt + li * 32 + kh * 16);
+      v16i acc;
+      for (int r = 0; r < 16; r++) acc[r] = 0;
+      acc = exchanged ? __builtin_amdgcn_mfma_i32_32x32x32_i8(b, a, acc, 0, 0, 0) : __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, acc, 0, 0, 0);
+      for (int r = 0; r < 16; r++) D[((r & 3) + 8 * (r >> 2) + 4 * kh) * 32 + li] = acc[r];
+   } else {
+      const int lj = lane & 15, qd = lane >> 4;
+      const v4i a = *reinterpret_cast<const v4i *>(A + lj * 64 + qd * 16), b = *reinterpret_cast<const v4i *>(Bt + lj * 64 + qd * 16);
+      v4i acc = {0, 0, 0, 0};
+      acc = exchanged ? __builtin_amdgcn_mfma_i32_16x16x64_i8(b, a, acc, 0, 0, 0) : __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, acc, 0, 0, 0);
+      for (int r = 0; r < 4; r++) D[(4 * qd + r) * 16 + lj] = acc[r];
+   }
+}
+
+void mfma_i8_ports(int shape, bool exchanged, const int8_t *A, const int8_t *Bt, int *D, hipStream_t stream)
+{
+   hipLaunchKernelGGL(k_mfma_i8_ports, dim3(1), dim3(64), 0, stream, shape, exchanged ? 1 : 0, A, Bt, D);
+   launch_check();
+}
+
 // issue-rate ceiling of v_mfma_i32_32x32x32_i8: 8 independent accumulators per wave, explicit registers (the compiler
-// must not reorder or shuffle them), operands = `fill` pattern (0: zeros, else pseudo-random bytes -- the rate is
-// power-limited, so the operand toggling matters)
-__global__ __launch_bounds__(256, 1) void k_mfma_i8_peak(int *out, int iters, uint32_t fill)
+// must not reorder or shuffle them).  The rate is power-limited, so what the operands hold and how often they change matters: each
+// port has two register sets (A: v128-131 / v132-135, B: v136-139 / v140-143), each filled by its own kind and seed (I8PeakFill).
+//   order 0: A alternates its sets every instruction, B holds one set for two   (A0 B0, A1 B0, A0 B1, A1 B1)
+//   order 1: A holds one set for two instructions, B alternates every one       (A0 B0, A0 B1, A1 B0, A1 B1)
+// (with equal sets nothing changes between instructions and the order is immaterial)
+#define I8_PEAK_CLOBBERS "v0", "v1", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9", "v10", "v11", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19", "v20", "v21", "v22", "v23", "v24", "v25", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", "v34", "v35", "v36", "v37", "v38", "v39", "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63", "v64", "v65", "v66", "v67", "v68", "v69", "v70", "v71", "v72", "v73", "v74", "v75", "v76", "v77", "v78", "v79", "v80", "v81", "v82", "v83", "v84", "v85", "v86", "v87", "v88", "v89", "v90", "v91", "v92", "v93", "v94", "v95", "v96", "v97", "v98", "v99", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112", "v113", "v114", "v115", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127", "v128", "v129", "v130", "v131", "v132", "v133", "v134", "v135", "v136", "v137", "v138", "v139", "v140", "v141", "v142", "v143"
+__global__ __launch_bounds__(256, 1) void k_mfma_i8_peak(int *out, int iters, I8PeakFill fl)
 {
    const uint32_t l = threadIdx.x * 2654435761u;
-   const uint32_t f0 = fill ? (fill ^ l) * 0x9E3779B1u : 0u, f1 = fill ? (f0 >> 3) * 0x85EBCA6Bu : 0u, f2 = fill ? (f1 >> 5) * 0xC2B2AE35u : 0u,
-                  f3 = fill ? (f2 >> 7) * 0x27D4EB2Fu : 0u;
+   uint32_t f[4][4]; // [A set 0, A set 1, B set 0, B set 1][dword]
+#pragma unroll
+   for (int s = 0; s < 4; s++) {
+      const uint32_t kind = fl.kind[s];
+      uint32_t h[4];
+      h[0] = (fl.seed[s] ^ l) * 0x9E3779B1u;
+      h[1] = (h[0] >> 3) * 0x85EBCA6Bu;
+      h[2] = (h[1] >> 5) * 0xC2B2AE35u;
+      h[3] = (h[2] >> 7) * 0x27D4EB2Fu;
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+         uint32_t g = 0; // I8_FILL_GENO: every hashed byte x becomes 3 x >> 8, a third each of 0, 1 and 2
+#pragma unroll
+         for (int k = 0; k < 4; k++) g |= ((((h[q] >> (8 * k)) & 0xffu) * 3u) >> 8) << (8 * k);
+         f[s][q] = kind == I8_FILL_ZERO ? 0u : kind == I8_FILL_GENO ? g : h[q];
+      }
+   }
    asm volatile(
       "v_mov_b32 v0, 0\n\t"
       "v_mov_b32 v1, 0\n\t"
@@ -1765,43 +1828,58 @@ __global__ __launch_bounds__(256, 1) void k_mfma_i8_peak(int *out, int iters, ui
       "v_mov_b32 v125, 0\n\t"
       "v_mov_b32 v126, 0\n\t"
       "v_mov_b32 v127, 0\n\t"
-      ::: "v0", "v1", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9", "v10", "v11", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19", "v20", "v21", "v22", "v23", "v24", "v25", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", "v34", "v35", "v36", "v37", "v38", "v39", "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63", "v64", "v65", "v66", "v67", "v68", "v69", "v70", "v71", "v72", "v73", "v74", "v75", "v76", "v77", "v78", "v79", "v80", "v81", "v82", "v83", "v84", "v85", "v86", "v87", "v88", "v89", "v90", "v91", "v92", "v93", "v94", "v95", "v96", "v97", "v98", "v99", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112", "v113", "v114", "v115", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127", "v128", "v129", "v130", "v131", "v132", "v133", "v134", "v135", "v136", "v137", "v138", "v139", "v140", "v141", "v142", "v143");
+      ::: I8_PEAK_CLOBBERS);
    asm volatile(
       "v_mov_b32 v128, %0\n\t"
       "v_mov_b32 v129, %1\n\t"
       "v_mov_b32 v130, %2\n\t"
       "v_mov_b32 v131, %3\n\t"
-      "v_mov_b32 v132, %0\n\t"
-      "v_mov_b32 v133, %1\n\t"
-      "v_mov_b32 v134, %2\n\t"
-      "v_mov_b32 v135, %3\n\t"
-      "v_mov_b32 v136, %0\n\t"
-      "v_mov_b32 v137, %1\n\t"
-      "v_mov_b32 v138, %2\n\t"
-      "v_mov_b32 v139, %3\n\t"
-      "v_mov_b32 v140, %0\n\t"
-      "v_mov_b32 v141, %1\n\t"
-      "v_mov_b32 v142, %2\n\t"
-      "v_mov_b32 v143, %3\n\t"
-      :: "v"(f0), "v"(f1), "v"(f2), "v"(f3) : "v0", "v1", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9", "v10", "v11", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19", "v20", "v21", "v22", "v23", "v24", "v25", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", "v34", "v35", "v36", "v37", "v38", "v39", "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63", "v64", "v65", "v66", "v67", "v68", "v69", "v70", "v71", "v72", "v73", "v74", "v75", "v76", "v77", "v78", "v79", "v80", "v81", "v82", "v83", "v84", "v85", "v86", "v87", "v88", "v89", "v90", "v91", "v92", "v93", "v94", "v95", "v96", "v97", "v98", "v99", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112", "v113", "v114", "v115", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127", "v128", "v129", "v130", "v131", "v132", "v133", "v134", "v135", "v136", "v137", "v138", "v139", "v140", "v141", "v142", "v143");
-   for (int it = 0; it < iters; it++) {
-      asm volatile(
-         "v_mfma_i32_32x32x32_i8 v[0:15], v[128:131], v[136:139], v[0:15]\n\t"
-         "v_mfma_i32_32x32x32_i8 v[16:31], v[132:135], v[136:139], v[16:31]\n\t"
-         "v_mfma_i32_32x32x32_i8 v[32:47], v[128:131], v[140:143], v[32:47]\n\t"
-         "v_mfma_i32_32x32x32_i8 v[48:63], v[132:135], v[140:143], v[48:63]\n\t"
-         "v_mfma_i32_32x32x32_i8 v[64:79], v[128:131], v[136:139], v[64:79]\n\t"
-         "v_mfma_i32_32x32x32_i8 v[80:95], v[132:135], v[136:139], v[80:95]\n\t"
-         "v_mfma_i32_32x32x32_i8 v[96:111], v[128:131], v[140:143], v[96:111]\n\t"
-         "v_mfma_i32_32x32x32_i8 v[112:127], v[132:135], v[140:143], v[112:127]\n\t"
-         ::: "v0", "v1", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9", "v10", "v11", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19", "v20", "v21", "v22", "v23", "v24", "v25", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", "v34", "v35", "v36", "v37", "v38", "v39", "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63", "v64", "v65", "v66", "v67", "v68", "v69", "v70", "v71", "v72", "v73", "v74", "v75", "v76", "v77", "v78", "v79", "v80", "v81", "v82", "v83", "v84", "v85", "v86", "v87", "v88", "v89", "v90", "v91", "v92", "v93", "v94", "v95", "v96", "v97", "v98", "v99", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112", "v113", "v114", "v115", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127", "v128", "v129", "v130", "v131", "v132", "v133", "v134", "v135", "v136", "v137", "v138", "v139", "v140", "v141", "v142", "v143");
-   }
+      "v_mov_b32 v132, %4\n\t"
+      "v_mov_b32 v133, %5\n\t"
+      "v_mov_b32 v134, %6\n\t"
+      "v_mov_b32 v135, %7\n\t"
+      "v_mov_b32 v136, %8\n\t"
+      "v_mov_b32 v137, %9\n\t"
+      "v_mov_b32 v138, %10\n\t"
+      "v_mov_b32 v139, %11\n\t"
+      "v_mov_b32 v140, %12\n\t"
+      "v_mov_b32 v141, %13\n\t"
+      "v_mov_b32 v142, %14\n\t"
+      "v_mov_b32 v143, %15\n\t"
+      :: "v"(f[0][0]), "v"(f[0][1]), "v"(f[0][2]), "v"(f[0][3]), "v"(f[1][0]), "v"(f[1][1]), "v"(f[1][2]), "v"(f[1][3]), "v"(f[2][0]), "v"(f[2][1]), "v"(f[2][2]), "v"(f[2][3]), "v"(f[3][0]), "v"(f[3][1]), "v"(f[3][2]), "v"(f[3][3]) : I8_PEAK_CLOBBERS);
+   if (fl.order == 0)
+      for (int it = 0; it < iters; it++) {
+         asm volatile(
+            "v_mfma_i32_32x32x32_i8 v[0:15], v[128:131], v[136:139], v[0:15]\n\t"
+            "v_mfma_i32_32x32x32_i8 v[16:31], v[132:135], v[136:139], v[16:31]\n\t"
+            "v_mfma_i32_32x32x32_i8 v[32:47], v[128:131], v[140:143], v[32:47]\n\t"
+            "v_mfma_i32_32x32x32_i8 v[48:63], v[132:135], v[140:143], v[48:63]\n\t"
+            "v_mfma_i32_32x32x32_i8 v[64:79], v[128:131], v[136:139], v[64:79]\n\t"
+            "v_mfma_i32_32x32x32_i8 v[80:95], v[132:135], v[136:139], v[80:95]\n\t"
+            "v_mfma_i32_32x32x32_i8 v[96:111], v[128:131], v[140:143], v[96:111]\n\t"
+            "v_mfma_i32_32x32x32_i8 v[112:127], v[132:135], v[140:143], v[112:127]\n\t"
+            ::: I8_PEAK_CLOBBERS);
+      }
+   else
+      for (int it = 0; it < iters; it++) {
+         asm volatile(
+            "v_mfma_i32_32x32x32_i8 v[0:15], v[128:131], v[136:139], v[0:15]\n\t"
+            "v_mfma_i32_32x32x32_i8 v[16:31], v[128:131], v[140:143], v[16:31]\n\t"
+            "v_mfma_i32_32x32x32_i8 v[32:47], v[132:135], v[136:139], v[32:47]\n\t"
+            "v_mfma_i32_32x32x32_i8 v[48:63], v[132:135], v[140:143], v[48:63]\n\t"
+            "v_mfma_i32_32x32x32_i8 v[64:79], v[128:131], v[136:139], v[64:79]\n\t"
+            "v_mfma_i32_32x32x32_i8 v[80:95], v[128:131], v[140:143], v[80:95]\n\t"
+            "v_mfma_i32_32x32x32_i8 v[96:111], v[132:135], v[136:139], v[96:111]\n\t"
+            "v_mfma_i32_32x32x32_i8 v[112:127], v[132:135], v[140:143], v[112:127]\n\t"
+            ::: I8_PEAK_CLOBBERS);
+      }
    int r;
-   asm volatile("s_nop 7\n\ts_nop 7\n\tv_mov_b32 %0, v0" : "=v"(r)::"v0", "v1", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9", "v10", "v11", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19", "v20", "v21", "v22", "v23", "v24", "v25", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", "v34", "v35", "v36", "v37", "v38", "v39", "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63", "v64", "v65", "v66", "v67", "v68", "v69", "v70", "v71", "v72", "v73", "v74", "v75", "v76", "v77", "v78", "v79", "v80", "v81", "v82", "v83", "v84", "v85", "v86", "v87", "v88", "v89", "v90", "v91", "v92", "v93", "v94", "v95", "v96", "v97", "v98", "v99", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112", "v113", "v114", "v115", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127", "v128", "v129", "v130", "v131", "v132", "v133", "v134", "v135", "v136", "v137", "v138", "v139", "v140", "v141", "v142", "v143");
+   asm volatile("s_nop 7\n\ts_nop 7\n\tv_mov_b32 %0, v0" : "=v"(r)::I8_PEAK_CLOBBERS);
    if (r == 0x7fffffff) out[threadIdx.x] = r;
 }
+#undef I8_PEAK_CLOBBERS
 
-double mfma_i8_peak_tops(int waves_per_simd, int iters, uint32_t fill, hipStream_t stream)
+double mfma_i8_peak_tops(int waves_per_simd, int iters, const I8PeakFill &fill, hipStream_t stream)
 {
    DevMem<int> d(1024, "fpca_debug_mfma_peak", "the probe's output words");
    const int blocks = 256 * waves_per_simd;

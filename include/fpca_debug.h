@@ -47,10 +47,17 @@ int fpca_debug_mfma_probe(const double *A, const double *B, double *D);
 /* diagnostic: D(32x32 int32, row-major) = A(32x32 int8, row-major) * Bt(32x32 int8, row j = column j of B)' through
  * v_mfma_i32_32x32x32_i8 with the lane->operand mapping of kernels_i8.hip; host pointers */
 int fpca_debug_mfma_i8_probe(const int8_t *A, const int8_t *Bt, int32_t *D);
+/* diagnostic: the two int8 instructions of the GEMM with their operands as above (exchanged = 0) or exchanged, stored through
+ * the register map of exchanged = 0 -- exchanged, D comes back transposed.  shape 32: v_mfma_i32_32x32x32_i8, A, Bt and D as
+ * above; shape 16: v_mfma_i32_16x16x64_i8, A(16x64) Bt(16x64)' = D(16x16).  Any other shape: FPCA_EINVAL.  Host pointers. */
+int fpca_debug_mfma_i8_ports(int shape, int exchanged, const int8_t *A, const int8_t *Bt, int32_t *D);
 /* diagnostic: sustained rate (TFLOP/s) of a pure v_mfma_f64_16x16x4_f64 stream with `waves_per_simd` (1..8) resident
  * waves per SIMD and no memory traffic; pattern 0..3 selects the operand-register sharing pattern (kernels.hip).  The
  * practical ceiling to read the GEMM kernels' roofline fraction against (72-74 TFLOP/s at 2 waves/SIMD vs 78.6 datasheet).
- * pattern 10 / 11: v_mfma_i32_32x32x32_i8 in TOP/s with zero / pseudo-random operands.  Any other pattern: FPCA_EINVAL. */
+ * pattern 10 / 11: v_mfma_i32_32x32x32_i8 in TOP/s with zero / pseudo-random operands.  12..17: the same stream with the two
+ * operand ports filled differently (source A / source B): 12 random / zero, 13 zero / random, 14 genotype bytes {0, 1, 2} / random,
+ * 15 random / genotype bytes; 16 as 14 with B changing every instruction and A every second (14, 15, 17: the reverse; 17 repeats
+ * 14's stream).  Any other pattern: FPCA_EINVAL. */
 int fpca_debug_mfma_peak(int waves_per_simd, int iters, int pattern, double *tflops);
 /* diagnostic (tests/test_gpu_kernels.py): the K4 helpers the eigensolver runs on its HBM-resident basis, on caller data and
  * through the very backend object the solver drives (HipBackend::gram incl. its split-K plane reduction, HipBackend::gemm).
