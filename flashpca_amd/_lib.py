@@ -205,6 +205,7 @@ SIGNATURES = {
     "fpca_debug_sample_qc_rule": (_I, [_P, _U64, _U64, _D, _P, C.POINTER(_U64)]),
     "fpca_debug_snp_qc_counts_rule": (_I, [_P, _P, _U64, _U64, _D, _D, _D, _P, C.POINTER(_U64)]),
     "fpca_bench_qc": (_I, [_P, _I, _P, C.POINTER(_D)]),
+    "fpca_debug_synth_host": (_I, [_U64, _U64, _U64, _U64, C.POINTER(SynthModel), _P, C.POINTER(_U64)]),
     "fpca_debug_scratch_live": (_I, [C.POINTER(_U64)]),
     "fpca_debug_scratch_fail_at": (_I, [_U64]),
 }

@@ -48,6 +48,23 @@ def _snp_mask(snps, P):
     return mask
 
 
+def _synth_model(n_pop, fst, missing_rate, realistic, maf_model, missing_model, conc_frac, lognormal_sigma):
+    return _lib.SynthModel(n_pop, fst, missing_rate, int(realistic if maf_model is None else maf_model),
+                           int(realistic if missing_model is None else missing_model), conc_frac, lognormal_sigma)
+
+
+def debug_synth_host(N, P, snp_begin=0, seed=20260928, n_pop=40, fst=0.05, missing_rate=0.001, realistic=False, maf_model=None,
+                     missing_model=None, conc_frac=0.05, lognormal_sigma=0.0):
+    """fpca_debug_synth_host: records [snp_begin, snp_begin + P) of the matrix Context.synthetic(N, ...) generates with the same
+    arguments, computed on the host (no device involved).  Returns (packed, fixed): a uint8 array of shape (P, (N + 3) // 4) and the
+    five integers the model was reduced to, as a dict (fst_fp, miss_thr, conc_fp, med_q32, sig2_fp)."""
+    m = _synth_model(n_pop, fst, missing_rate, realistic, maf_model, missing_model, conc_frac, lognormal_sigma)
+    out = np.empty((int(P), (int(N) + 3) // 4), dtype=np.uint8)
+    fixed = (C.c_uint64 * 5)()
+    check(lib().fpca_debug_synth_host(N, snp_begin, P, seed, C.byref(m), _p(out), fixed))
+    return out, dict(zip(("fst_fp", "miss_thr", "conc_fp", "med_q32", "sig2_fp"), (int(v) for v in fixed)))
+
+
 class Context:
     def __init__(self, handle, accum="auto"):
         self.h = handle
@@ -106,10 +123,11 @@ class Context:
     def synthetic(cls, N, P, snp_begin=0, seed=20260928, n_pop=40, fst=0.05, missing_rate=0.001, stand="binom2", device=0,
                   accum="fp64", realistic=False, maf_model=None, missing_model=None, conc_frac=0.05, lognormal_sigma=0.0):
         """realistic=True: the round-4 profile (synth.hpp) -- rare-variant allele-frequency spectrum, missing calls concentrated in
-        5 % of the SNPs (maf_model / missing_model = 1; either can be chosen alone)."""
+        5 % of the SNPs (maf_model / missing_model = 1; either can be chosen alone).  missing_model=2: per-SNP rates log-normally
+        distributed with log-sd lognormal_sigma; missing_rate is the NOMINAL mean -- the realised mean of the per-SNP thresholds is
+        0.87-1.00 of it (the tail is cut), see profiles/synth_model_figures.txt."""
         h = C.c_void_p()
-        m = _lib.SynthModel(n_pop, fst, missing_rate, int(realistic if maf_model is None else maf_model),
-                            int(realistic if missing_model is None else missing_model), conc_frac, lognormal_sigma)
+        m = _synth_model(n_pop, fst, missing_rate, realistic, maf_model, missing_model, conc_frac, lognormal_sigma)
         check(lib().fpca_create_synthetic_model(C.byref(h), N, snp_begin, P, seed, C.byref(m), STANDARDISE[stand], device, ACCUM[accum]))
         return cls(h, accum)
 

@@ -209,30 +209,96 @@ int fpca_create_synthetic(fpca_ctx **out, uint64_t N, uint64_t snp_begin, uint64
    return fpca_create_synthetic_model(out, N, snp_begin, P_g, seed, &m, stand_method, device, accum);
 }
 
+namespace {
+// what a fpca_synth_model is reduced to before a record is generated: the integers of synth.hpp
+struct SynthFixed {
+   int n_pop, maf_model, missing_model;
+   uint32_t fst_fp, miss_thr, conc_fp, sig2_fp;
+   uint64_t med_q32;
+};
+
+// the argument checks and the double -> fixed-point conversion of the synthetic model, for the device generator
+// (fpca_create_synthetic_model) and the host one (fpca_debug_synth_host) alike; touches no device
+SynthFixed synth_reduce(const fpca_synth_model *model)
+{
+   if (!model) throw Error(FPCA_EINVAL, "model is NULL");
+   const int n_pop = model->n_pop;
+   const double fst = model->fst, missing_rate = model->missing_rate;
+   if (n_pop < 1 || n_pop > synth::MAX_POP) throw Error(FPCA_EINVAL, "n_pop must be in 1..64");
+   if (!(fst >= 0 && fst < 1) || !(missing_rate >= 0 && missing_rate < 1)) throw Error(FPCA_EINVAL, "fst / missing_rate out of range");
+   if ((model->maf_model | 1) != 1 || model->missing_model < 0 || model->missing_model > 2 || !(model->conc_frac >= 0 && model->conc_frac <= 1))
+      throw Error(FPCA_EINVAL, "maf_model must be 0 or 1, missing_model 0, 1 or 2, conc_frac in [0, 1]");
+   if (model->missing_model == 2 && !(model->lognormal_sigma >= 0 && model->lognormal_sigma <= 4))
+      throw Error(FPCA_EINVAL, "lognormal_sigma must be in [0, 4]");
+   SynthFixed f;
+   f.n_pop = n_pop;
+   f.maf_model = model->maf_model;
+   f.missing_model = model->missing_model;
+   f.fst_fp = (uint32_t)std::llround(fst * 65536.0);
+   f.miss_thr = (uint32_t)std::llround(missing_rate * 65536.0);
+   f.conc_fp = (uint32_t)std::llround(model->conc_frac * 65536.0);
+   // log-normal rates: the median that gives the asked-for mean, in 0.32 fixed point; sigma as a power of two (host libm only sets
+   // these two integers: the matrix itself is integer arithmetic, identical on every host and device)
+   const double sig = model->missing_model == 2 ? model->lognormal_sigma : 0.0;
+   f.med_q32 = (uint64_t)std::llround(std::min(missing_rate * std::exp(-0.5 * sig * sig), 0.9) * 4294967296.0);
+   f.sig2_fp = (uint32_t)std::llround(sig / std::log(2.0) * 65536.0);
+   return f;
+}
+} // namespace
+
 int fpca_create_synthetic_model(fpca_ctx **out, uint64_t N, uint64_t snp_begin, uint64_t P_g, uint64_t seed, const fpca_synth_model *model,
                                 int stand_method, int device, int accum)
 {
    return create_ctx(out, [&](fpca_ctx *c) {
-      if (!model) throw Error(FPCA_EINVAL, "model is NULL");
-      const int n_pop = model->n_pop;
-      const double fst = model->fst, missing_rate = model->missing_rate;
-      if (n_pop < 1 || n_pop > synth::MAX_POP) throw Error(FPCA_EINVAL, "n_pop must be in 1..64");
-      if (!(fst >= 0 && fst < 1) || !(missing_rate >= 0 && missing_rate < 1)) throw Error(FPCA_EINVAL, "fst / missing_rate out of range");
-      if ((model->maf_model | 1) != 1 || model->missing_model < 0 || model->missing_model > 2 || !(model->conc_frac >= 0 && model->conc_frac <= 1))
-         throw Error(FPCA_EINVAL, "maf_model must be 0 or 1, missing_model 0, 1 or 2, conc_frac in [0, 1]");
-      if (model->missing_model == 2 && !(model->lognormal_sigma >= 0 && model->lognormal_sigma <= 4))
-         throw Error(FPCA_EINVAL, "lognormal_sigma must be in [0, 4]");
+      const SynthFixed f = synth_reduce(model);
       ctx_alloc_common(c, N, P_g, stand_method, device, accum);
-      const uint32_t fst_fp = (uint32_t)std::llround(fst * 65536.0);
-      const uint32_t miss_thr = (uint32_t)std::llround(missing_rate * 65536.0);
-      // log-normal rates: the median that gives the asked-for mean, in 0.32 fixed point; sigma as a power of two (host libm only sets
-      // these two integers: the matrix itself is integer arithmetic, identical on every host and device)
-      const double sig = model->missing_model == 2 ? model->lognormal_sigma : 0.0;
-      const uint64_t med_q32 = (uint64_t)std::llround(std::min(missing_rate * std::exp(-0.5 * sig * sig), 0.9) * 4294967296.0);
-      const uint32_t sig2_fp = (uint32_t)std::llround(sig / std::log(2.0) * 65536.0);
-      kern::synth_generate(c->d_packed, c->pitch, N, snp_begin, P_g, seed, n_pop, fst_fp, miss_thr, c->stream, model->maf_model, model->missing_model,
-                           (uint32_t)std::llround(model->conc_frac * 65536.0), med_q32, sig2_fp);
+      kern::synth_generate(c->d_packed, c->pitch, N, snp_begin, P_g, seed, f.n_pop, f.fst_fp, f.miss_thr, c->stream, f.maf_model, f.missing_model,
+                           f.conc_fp, f.med_q32, f.sig2_fp);
       HIP_CHECK(hipStreamSynchronize(c->stream));
+   });
+}
+
+int fpca_debug_synth_host(uint64_t N, uint64_t snp_begin, uint64_t P_g, uint64_t seed, const fpca_synth_model *model, uint8_t *out,
+                          uint64_t fixed[5])
+{
+   return guarded([&] {
+      const SynthFixed f = synth_reduce(model);
+      if (N == 0 || N >= (1ull << 40)) throw Error(FPCA_EINVAL, "N must be in 1 .. 2^40 - 1");
+      if (!out && P_g > 0) throw Error(FPCA_EINVAL, "out is NULL");
+      if (fixed) {
+         fixed[0] = f.fst_fp;
+         fixed[1] = f.miss_thr;
+         fixed[2] = f.conc_fp;
+         fixed[3] = f.med_q32;
+         fixed[4] = f.sig2_fp;
+      }
+      const uint64_t np = (N + 3) / 4;
+      uint32_t thr[synth::MAX_POP];
+      uint64_t bnd[synth::MAX_POP + 1];
+      for (int c = 0; c <= f.n_pop; c++) bnd[c] = synth::pop_boundary(N, f.n_pop, c);
+      for (uint64_t r = 0; r < P_g; r++) {
+         const uint64_t snp = snp_begin + r;
+         const uint32_t pj = f.maf_model == 1 ? synth::snp_freq_rare(seed, snp) : synth::snp_freq(seed, snp);
+         uint32_t miss_thr = f.miss_thr;
+         if (f.missing_model == 1) miss_thr = synth::snp_miss_thr_concentrated(seed, snp, f.conc_fp);
+         if (f.missing_model == 2) miss_thr = synth::snp_miss_thr_lognormal(seed, snp, f.med_q32, f.sig2_fp);
+         for (int c = 0; c < f.n_pop; c++) thr[c] = synth::pop_freq(seed, snp, pj, f.fst_fp, c);
+         uint8_t *rec = out + r * np;
+         int pop = 0; // samples in ascending order: the population only moves forward, over empty ones too
+         for (uint64_t i = 0; i < np; i++) {
+            uint32_t byte = 0;
+            for (int s = 0; s < 4; s++) {
+               const uint64_t smp = 4 * i + s;
+               uint32_t code = 1u; // pad samples of the last byte = missing
+               if (smp < N) {
+                  while (pop + 1 < f.n_pop && smp >= bnd[pop + 1]) pop++;
+                  code = synth::cell_code(seed, snp, smp, thr[pop], miss_thr);
+               }
+               byte |= code << (2 * s);
+            }
+            rec[i] = (uint8_t)byte;
+         }
+      }
    });
 }
 

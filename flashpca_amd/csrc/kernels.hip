@@ -1825,7 +1825,8 @@ void colmajor_to_t(const double *in, uint64_t ld, uint64_t P_g, uint64_t P_pad, 
 
 // ------------------------------------------------------------------------------------------------
 // synthetic genotypes straight into HBM: one workgroup per SNP record, one 32-bit word (16 samples) per
-// thread per iteration; integer-only model of synth.hpp, so the host can reproduce any record bit for bit.
+// thread per iteration; integer-only model of synth.hpp, so the host can reproduce any record bit for bit
+// (fpca_debug_synth_host does; tests/test_gpu_synth.py compares).
 __global__ __launch_bounds__(256) void k_synth_generate(uint8_t *packed, size_t pitch, uint64_t N, uint64_t snp_begin,
                                                          uint64_t seed, int n_pop, uint32_t fst_fp, uint32_t miss_thr, int maf_model,
                                                          int missing_model, uint32_t conc_fp, uint64_t med_q32, uint32_t sig2_fp)

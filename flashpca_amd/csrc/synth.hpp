@@ -3,7 +3,8 @@
 // SURVEY.md section 8(d) asks for a structured (Balding-Nichols-like) population model so that the top-k
 // eigenvalues separate from the bulk, generated with a counter-based RNG so that any SNP range can be
 // produced independently on any rank.  Everything here is INTEGER arithmetic (16.16 fixed point), so the
-// host and the GPU produce bit-identical matrices with no dependence on libm or FMA contraction:
+// host and the GPU produce bit-identical matrices with no dependence on libm or FMA contraction
+// (fpca_debug_synth_host is the host generator; tests/test_gpu_synth.py holds the kernel to a replica of this description):
 //
 //   populations      n_pop sub-populations with unequal sizes: weight of population c is (c+1), samples
 //                    are assigned contiguously (boundaries[c] = N * c(c+1)/2 / (n_pop(n_pop+1)/2))
@@ -96,6 +97,9 @@ FPCA_HD uint32_t snp_miss_thr_concentrated(uint64_t seed, uint64_t snp, uint32_t
 // SNP the same rate" (model 0) and "5 % of the SNPs hold nearly all of it" (model 1): rate_j = median * 2^(sig2 z_j), z_j the
 // Irwin-Hall normal of pop_freq, capped at 0.9.  med_q32 = median rate in 0.32 fixed point, sig2_fp = sigma / ln 2 in 16.16;
 // 2^f for the fractional part by a cubic whose coefficients sum to one (2^0 = 1 and 2^1 = 2 exactly, 2e-4 relative in between).
+// The caller sets the median to mean exp(-sigma^2 / 2); that mean is nominal: the normal ends at 6 sd, the rate is capped and the
+// 16-bit threshold floors small rates -- nominal mean; realised mean of the thresholds 0.87-1.00 of it, see
+// profiles/synth_model_figures.txt.  The rate saturates at e >= 20 whatever the median, a median of 0 included.
 FPCA_HD uint32_t snp_miss_thr_lognormal(uint64_t seed, uint64_t snp, uint64_t med_q32, uint32_t sig2_fp)
 {
    int64_t zsum = 0;

@@ -112,12 +112,15 @@ int fpca_create_synthetic(fpca_ctx **out, uint64_t N, uint64_t snp_begin, uint64
  * (flashpca_amd/csrc/synth.hpp): maf_model 1 = rare-variant spectrum (minor-allele frequency 0.001 + 0.499 u^3: per-SNP sd over a
  * 16x range, SNPs monomorphic in small samples); missing_model 1 = missing calls concentrated in `conc_frac` of the SNPs (10-30 %
  * of their calls; every other SNP <= 0.1 %; missing_rate is ignored); missing_model 2 = per-SNP rates log-normally distributed
- * with MEAN missing_rate and log-sd lognormal_sigma (capped at 90 %): most SNPs below the mean, a long tail of poor assays.
+ * with log-sd lognormal_sigma (capped at 90 %): most SNPs below the mean, a long tail of poor assays.  missing_rate is the NOMINAL
+ * mean: the median is missing_rate exp(-sigma^2 / 2), but the tail that carries the rest of the mean is cut (the normal ends at 6 sd,
+ * the 90 % cap, 16-bit thresholds floor small rates) -- nominal mean; realised mean of the thresholds 0.87-1.00 of it, see
+ * profiles/synth_model_figures.txt.
  * maf_model = missing_model = 0 is fpca_create_synthetic. */
 typedef struct fpca_synth_model {
    int n_pop;            /* sub-populations (1..64): n_pop - 1 structured eigenvalues */
    double fst;
-   double missing_rate;  /* missing_model 0: every call; 2: the mean over SNPs */
+   double missing_rate;  /* missing_model 0: every call; 2: the nominal mean over SNPs (above) */
    int maf_model, missing_model;
    double conc_frac;     /* missing_model 1: fraction of SNPs with 10-30 % missing calls (e.g. 0.05) */
    double lognormal_sigma; /* missing_model 2: sd of ln(rate) over SNPs (e.g. 1.5) */

@@ -237,6 +237,16 @@ int fpca_debug_snp_qc_counts_rule(const uint32_t *counts, const double *p_hwe, u
  * one HWE launch makes at most. */
 int fpca_bench_qc(fpca_ctx *ctx, int reps, double *ms, double *hwe_steps);
 
+/* diagnostic (tests/test_synth_cpu.py, tests/test_gpu_synth.py): the synthetic genotype model of fpca_create_synthetic_model on the
+ * HOST, from the functions of csrc/synth.hpp alone -- no device involved, no HIP call made.  Writes records [snp_begin, snp_begin + P_g)
+ * of the (N, seed, model) matrix into out, (N + 3) / 4 bytes each, .bed body layout.  The pad samples of a record's last byte are code
+ * 01, as the kernel writes them into the resident matrix (fpca_download_packed hands them out as 00, as PLINK writes them: compare
+ * after clearing them).  fixed (may be NULL): the five integers the model's doubles are reduced to before anything is
+ * generated -- fst_fp (16.16), miss_thr (0.16), conc_fp (0.16), med_q32 (0.32), sig2_fp (16.16) -- by the very function the device
+ * entry takes them from.  Refuses what fpca_create_synthetic_model refuses of a model, N outside 1 .. 2^40 - 1, and a NULL out. */
+int fpca_debug_synth_host(uint64_t N, uint64_t snp_begin, uint64_t P_g, uint64_t seed, const fpca_synth_model *model, uint8_t *out,
+                          uint64_t fixed[5]);
+
 /* diagnostic (tests/test_gpu_scratch.py), builds with -DFPCA_TEST_HOOKS only: what the entry points hold for the length of one call --
  * device memory, pinned host memory, events (csrc/dev_scratch.hpp) -- is counted, and one acquisition can be made to fail.
  *   fpca_debug_scratch_live     out[0..2] = live device allocations, pinned allocations, events made through those owners: equal before

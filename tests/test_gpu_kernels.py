@@ -4,9 +4,13 @@ relative to the column norm (fp64 accumulation order differs between an MFMA tre
 """
 import json
 import os
+import sys
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import synth_yardstick  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -393,7 +397,14 @@ def test_missing_route_follows_the_cost_model_on_lognormal_rates(mean, sigma, ex
         X = od.dense()
         codes = np.stack([(packed.reshape(P, -1) >> (2 * s)) & 3 for s in range(4)], axis=-1).reshape(P, -1)[:, :N]
         rate = (codes == 1).mean(axis=1)
-        assert abs(rate.mean() - mean) < 0.25 * mean and (sigma < 1 or rate.max() > 8 * np.median(rate))  # the profile is what it says
+        # the profile is what it says: the realised rate is the mean of the per-SNP thresholds of this very call (the replica of
+        # tests/synth_yardstick.py; 0.88-1.00 of the nominal mean, profiles/synth_model_figures.txt) to binomial error -- N P cells,
+        # each missing with its SNP's probability q: four sd of the mean of the per-SNP rates
+        q = synth_yardstick.thresholds(P, n_pop=6, missing_rate=mean, missing_model=2, lognormal_sigma=sigma).miss / 65536.0
+        print("log-normal mean %g sigma %g: realised rate %.6f, mean threshold %.6f, binomial sd %.2e" % (
+            mean, sigma, rate.mean(), q.mean(), np.sqrt(np.sum(q * (1 - q)) / N) / P))
+        assert abs(rate.mean() - q.mean()) <= 4 * np.sqrt(np.sum(q * (1 - q)) / N) / P
+        assert sigma < 1 or rate.max() > 8 * np.median(rate)
         assert ctx.missing_mode(16) == expect, (ctx.missing_mode(16), rate.mean(), float(np.mean(rate > 0.0069)))
         if expect == 4:
             assert np.mean(rate > 0.0069) > (0.3 if mean >= 0.02 else 0.15)  # (round 4 admitted a dense set of at most a quarter, and only with the rest below 0.5 %)
