@@ -208,6 +208,7 @@ SIGNATURES = {
     "fpca_debug_synth_host": (_I, [_U64, _U64, _U64, _U64, C.POINTER(SynthModel), _P, C.POINTER(_U64)]),
     "fpca_debug_scratch_live": (_I, [C.POINTER(_U64)]),
     "fpca_debug_scratch_fail_at": (_I, [_U64]),
+    "fpca_debug_set_pass_slices": (_I, [_P, _I]),
 }
 
 ABI_VERSION = 4  # FPCA_ABI_VERSION of the include/fpca.h the structures above mirror

@@ -81,6 +81,11 @@ class Context:
         missing calls); -1 for the fp64 / fp32 kernels."""
         return int(lib().fpca_missing_mode(self.h, b))
 
+    def debug_pass_slices(self, Sc):
+        """fpca_debug_set_pass_slices (test-hook build): the next apply_xt / apply_x / apply_xxt run on Sc slices inside this context, as
+        the eigensolver's cheap passes do; 0: exact passes again.  pca() clears the setting."""
+        check(lib().fpca_debug_set_pass_slices(self.h, int(Sc)))
+
     def allreduce_chunks(self):
         """Row chunks of Y whose all-reduce overlaps the computation of the next chunk (fpca_allreduce_chunks)."""
         return int(lib().fpca_allreduce_chunks(self.h))

@@ -667,6 +667,25 @@ int fpca_debug_scratch_fail_at(uint64_t n)
    });
 }
 
+// the slice count of the next passes: the field HipBackend::set_cheap sets around the eigensolver's cheap passes
+int fpca_debug_set_pass_slices(fpca_ctx *ctx, int Sc)
+{
+   return guarded([&] {
+#ifdef FPCA_TEST_HOOKS
+      if (!ctx) throw Error(FPCA_EINVAL, "fpca_debug_set_pass_slices: ctx is NULL");
+      if (ctx->i8_S <= 0 || ctx->i8_k2_only)
+         throw Error(FPCA_EINVAL, "fpca_debug_set_pass_slices: the context does not run both products in the exact-integer arithmetic");
+      if (Sc != 0 && (Sc < 2 || Sc >= ctx->i8_S_req))
+         throw Error(FPCA_EINVAL, "fpca_debug_set_pass_slices: Sc must be 0 or from 2 to one below the context's slice count");
+      ctx->i8_Sc = Sc;
+#else
+      (void)ctx;
+      (void)Sc;
+      throw Error(FPCA_EINVAL, "fpca_debug_set_pass_slices: this is the product build; no pass changes its slice count without -DFPCA_TEST_HOOKS");
+#endif
+   });
+}
+
 int fpca_debug_mfma_peak(int waves_per_simd, int iters, int pattern, double *tflops)
 {
    return guarded([&] {

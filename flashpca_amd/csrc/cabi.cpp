@@ -391,6 +391,13 @@ int fpca_missing_mode(fpca_ctx *ctx, int b)
       if (!ctx || b < 1 || b > MAX_BLOCKVEC) throw Error(FPCA_EINVAL, "bad argument to fpca_missing_mode");
       HIP_CHECK(hipSetDevice(ctx->device));
       ensure_stats(ctx);
+      // the route of the EXACT passes, whatever slice count the passes being made now run on (i8_mode chooses per pass)
+      struct ExactPass {
+         fpca_ctx *c;
+         int Sc;
+         explicit ExactPass(fpca_ctx *c_) : c(c_), Sc(c_->i8_Sc) { c->i8_Sc = 0; }
+         ~ExactPass() { c->i8_Sc = Sc; }
+      } exact(ctx);
       mode = ctx->i8_S ? i8_mode(ctx, (int)round_up((uint64_t)b, 16)) : -1;
    });
    return rc == FPCA_OK ? mode : rc;

@@ -256,6 +256,15 @@ int fpca_debug_synth_host(uint64_t N, uint64_t snp_begin, uint64_t P_g, uint64_t
  * In the product build both return FPCA_EINVAL with a message that says so and do nothing: no switch changes what it computes. */
 int fpca_debug_scratch_live(uint64_t out[3]);
 int fpca_debug_scratch_fail_at(uint64_t n);
+/* diagnostic (tests/test_gpu_i8_cheap_passes.py), builds with -DFPCA_TEST_HOOKS only: the slice count of the context's NEXT products in
+ * the exact-integer arithmetic -- fpca_apply_xt, fpca_apply_x, fpca_apply_xxt run on Sc slices inside the context made for more, the state
+ * the eigensolver's cheap passes put it in (the very field HipBackend::set_cheap sets).  Sc = 0 clears it: the passes are exact again.
+ * fpca_missing_mode keeps reporting the route of the exact passes.  fpca_pca clears the setting: the solver's backend object sets the
+ * field for its own passes and leaves it at 0 when it goes (~HipBackend).
+ * FPCA_EINVAL, with a message that names the reason, unless the context runs both products in the exact-integer arithmetic and Sc is 0
+ * or 2 <= Sc < the slice count the context was created with.  In the product build it returns FPCA_EINVAL with a message that says so
+ * and does nothing: no switch changes what it computes. */
+int fpca_debug_set_pass_slices(fpca_ctx *ctx, int Sc);
 
 #ifdef __cplusplus
 }

@@ -5,11 +5,14 @@ so that the GPU comparison is np.array_equal -- with operands that live in the L
 Genotypes (stand="binom").  k_bed_stats computes mean = (2 n00 + n10) / ngood and sd = sqrt(pp (1 - pp)), pp = mean / 2.  A SNP whose
 called samples hold as many dosage-0 as dosage-2 calls has mean == 1.0 and sd == 0.5 exactly, whatever its heterozygotes: the standardised
 matrix is 2 g - 2 in {-2, 0, 2}, 0 for a missing call.  Every SNP is of that kind but one monomorphic SNP (sd 0: a zero row) and, in the
-sets that say so, one SNP without a call (mean and sd NaN: a zero row).  Four sets:
+sets that say so, one SNP without a call (mean and sd NaN: a zero row).  Five sets:
   D0  nothing missing                                           route 2
   D1  0 .. 3 missing calls per SNP (0.12 %)                     route 3 for b 16 / 32 / 64; routes 0 and 1 forced
   D2  5 % of the SNPs at 20 %, the others at most one           route 4 (for b 16 / 32 / 64: the list routes have no 48-column gather)
   D3  D1, one SNP without a call, dyadic mean / sd per SNP      the two-matrix kernels, mode 0 (fpca_set_meansd)
+  D4  2, 3, 3 or 4 missing calls per ordinary SNP (0.424 %)     route 3 in a context of 6 .. 8 slices (b 16 / 32 / 64) -- but a pass of
+                                                                that context on at most 4 slices takes the two-matrix kernels
+                                                                (`pass_route`: the cheap passes' break-even is 0.35 %, not 0.5 %)
 `route` is hybrid_classify / i8_mode of missing_routes.hip restated; D1's counts are what keeps it on route 3 at every S (with two or three
 calls in most SNPs the per-SNP rule of the hybrid route would take the shard at S = 2 and 3: 0.12 % rather than 0.2 %).
 
@@ -48,6 +51,8 @@ PIN_SAMPLE, PIN_SNP = 300, 270   # the pin rows r, r + 1 (r even: the same 16-ro
 MONO_SNP, NOCALL_SNP = 5, 400
 CODE = {2: 0, "missing": 1, 1: 2, 0: 3}  # dosage -> raw 2-bit code
 D_CELL, G_CALL, M2_CELL, SPARSE_BREAK_EVEN = 1.96e-15, 2.0e-12, 1.45e-15, 0.005  # missing_routes.hip
+CHEAP_SPARSE_BREAK_EVEN = 0.0035                                                 # ... and the cheap passes' own break-even
+LIST_SETS = ("D1", "D2", "D4")  # the sets whose own route has index lists: at <= 4 slices the gathers read fp32 rows
 
 
 # ---- genotypes ---------------------------------------------------------------------------------------------------------------------------
@@ -77,8 +82,8 @@ def _balanced_row(rng, n, called):
 
 @functools.lru_cache(maxsize=None)
 def genotypes(name, n=N, p=P):
-    """codes [p][n] uint8 (raw: 0 dosage 2, 1 missing, 2 dosage 1, 3 dosage 0) of data set D0 .. D3."""
-    rng = np.random.default_rng({"D0": 11, "D1": 12, "D2": 13, "D3": 12}[name] + 1000 * n)
+    """codes [p][n] uint8 (raw: 0 dosage 2, 1 missing, 2 dosage 1, 3 dosage 0) of data set D0 .. D4."""
+    rng = np.random.default_rng({"D0": 11, "D1": 12, "D2": 13, "D3": 12, "D4": 14}[name] + 1000 * n)
     nmiss = np.zeros(p, dtype=int)
     if name in ("D1", "D3"):
         c2, c3 = p * 30 // 523, p * 13 // 523
@@ -89,6 +94,9 @@ def genotypes(name, n=N, p=P):
         nmiss = (rng.random(p) < 0.5).astype(int)
         ordinary = np.setdiff1d(np.arange(p), [MONO_SNP, PIN_SNP, PIN_SNP + 1, NOCALL_SNP])
         nmiss[rng.choice(ordinary, size=p // 20, replace=False)] = n // 5
+    elif name == "D4":
+        ordinary = np.setdiff1d(np.arange(p), [MONO_SNP, PIN_SNP, PIN_SNP + 1, NOCALL_SNP])
+        nmiss[ordinary] = rng.permutation(np.resize([2, 3, 3, 4], ordinary.size))
     nmiss[[MONO_SNP, PIN_SNP, PIN_SNP + 1, NOCALL_SNP]] = 0
     free = np.setdiff1d(np.arange(n), [PIN_SAMPLE, PIN_SAMPLE + 1])
     codes = np.empty((p, n), dtype=np.uint8)
@@ -185,7 +193,7 @@ def operand_kind(name, S):
     """'full', or the window width W: see the module docstring."""
     if S >= 6:
         return 5
-    if S == 4 and name in ("D1", "D2"):
+    if S == 4 and name in LIST_SETS:
         return 3  # the list routes read fp32 rows at S <= 4: 24 significant bits
     return "full"
 
@@ -415,10 +423,270 @@ def expected_mode(run):
 
 
 def data_keys():
-    """Every (ds, S, b, op, tall) whose operands some GPU case multiplies."""
+    """Every (ds, S, b, op, tall) whose operands some GPU case multiplies (a pass on Sc slices multiplies the operands made for Sc)."""
     keys = set()
     for child in CHILDREN:
         for r in child_runs(child):
             for op in ("xt", "x"):
                 keys.add((r["ds"], r["S"], r["b"], op, r["tall"]))
+    for child in CHEAP_CHILDREN:
+        for r in cheap_runs(child):
+            for op in ("xt", "x"):
+                keys.add((r["ds"], r["Sc"], r["b"], op, r["tall"]))
     return sorted(keys)
+
+
+# ---- passes on fewer slices than the context holds (tests/test_gpu_i8_cheap_passes.py; checked by tests/test_i8_planes_cpu.py) ----------
+# The eigensolver's cheap passes run K2 and K3 on Sc < S slices inside the context made for S (fpca_ctx::i8_Sc), exact passes between
+# them.  A run here is dict(ds, S = the context's slices, Sc = the slices of this pass, b, tiled, mode, tall, q = its place in the
+# context's sequence); Sc == S is an exact pass.  Its operand is case_operand(ds, Sc, ...), its reference that operand's: neither
+# depends on S.
+@functools.lru_cache(maxsize=None)
+def nmiss_of(name, n=N, p=P):
+    return (dosage_called(genotypes(name, n, p))[1] == 0).sum(axis=1)
+
+
+def pass_route(nmiss, n, S_ctx, Sc, b):
+    """The route of ONE pass: `route` of the context, but a pass on at most 4 slices of a context that holds more leaves the lists for
+    the two-matrix kernels above the cheap passes' own break-even (i8_mode of missing_routes.hip, its last rule before I8M_SPARSE).  The
+    cost model of the hybrid classification keeps the context's slice count."""
+    nmiss = np.asarray(nmiss, dtype=np.int64)
+    r = route(nmiss, n, S_ctx, b)
+    if r == 3 and Sc < S_ctx and Sc <= 4 and int(nmiss.sum()) / (n * nmiss.size) > CHEAP_SPARSE_BREAK_EVEN:
+        return 0
+    return r
+
+
+CHEAP_CHILDREN = {"cheap7": (7, (None, 0)), "cheap8": (8, (None,)), "cheap6": (6, (None,))}  # child -> context slices, layouts
+CHEAP_SETS = (("D0", None), ("D1", None), ("D2", None), ("D4", None), ("D3", 0))
+# The default layout: the pass is the outer loop -- (slices, the width the pass starts at; the widths go round from there).
+PASSES = {7: ((7, 16), (4, 16), (7, 16), (3, 16), (6, 32), (4, 16), (5, 16), (2, 16), (7, 16)),
+          8: ((8, 16), (3, 16), (5, 16), (4, 16), (8, 32), (2, 16), (7, 16), (8, 16)),
+          6: ((6, 16), (4, 16), (5, 16), (3, 16), (6, 32), (2, 16), (6, 16))}
+# FPCA_I8_TILED=0: the width is the outer loop -- (width, the passes at it); shortened.
+PASSES_RM = {7: ((16, (7, 4, 6)), (32, (3, 7, 5)), (48, (5,)), (64, (5, 2, 7)))}
+
+
+def pass_sequence(S_ctx, tiled, ds):
+    """[(Sc, b)] one context runs, in order."""
+    widths = [b for b in WIDTHS if not (b == 48 and ds in LIST_SETS)]  # (the list routes have gather kernels for 16 / 32 / 64 columns)
+    if tiled is not None:
+        return [(Sc, b) for b, scs in PASSES_RM[S_ctx] if b in widths for Sc in scs]
+    seq = []
+    for Sc, b0 in PASSES[S_ctx]:
+        k = widths.index(b0)
+        seq += [(Sc, b) for b in widths[k:] + widths[:k]]
+    return seq
+
+
+def cheap_runs(child):
+    """The runs of a child of tests/test_gpu_i8_cheap_passes.py; consecutive runs of one (ds, tiled) share one context."""
+    S_ctx, layouts = CHEAP_CHILDREN[child]
+    return [dict(ds=ds, S=S_ctx, Sc=Sc, b=b, tiled=tiled, mode=mode, tall=False, q=q)
+            for tiled in layouts for ds, mode in CHEAP_SETS for q, (Sc, b) in enumerate(pass_sequence(S_ctx, tiled, ds))]
+
+
+def pass_run_id(run):
+    return "%s-S%d-%s-m%s-q%02d-c%d-b%d" % (run["ds"], run["S"], "tl" if run["tiled"] is None else "rm", "d" if run["mode"] is None else run["mode"],
+                                            run["q"], run["Sc"], run["b"])
+
+
+def expected_pass_modes(run):
+    """(what fpca_missing_mode answers: the exact passes' route; the route of this pass)."""
+    if run["mode"] is not None:
+        return run["mode"], run["mode"]
+    n, p = dims(run["tall"])
+    nm = nmiss_of(run["ds"], n, p)
+    return route(nm, n, run["S"], run["b"]), pass_route(nm, n, run["S"], run["Sc"], run["b"])
+
+
+# The witness.  The operands of a pass on Sc slices are exact at Sc, hence exact at S too: a hook that changed nothing would pass every
+# comparison.  So every run and product applies one more block:
+#   Sc < S   block 0 with a quarter of the Sc quantum, 2^(e_c - F_Sc - 2), taken off the magnitude of a few entries (added to a zero).
+#            On Sc slices the quarter rounds away -- m = rint(m0 -+ 1/4) = m0, the column maximum and with it e_c are untouched -- so
+#            the result equals block 0's bit for bit; on the context's S slices (8 (S - Sc) more bits) the quarter is a digit.
+#   Sc == S  block 0 on a grid three bits finer, n' = 8 n + w at unit - 3, w = 1 in the witness entries of the columns whose window
+#            starts above digit 0 (there unit - 3 is still on the S grid): exact at S, compared with its own int64 reference, and
+#            different from block 0's.  (That an exact pass runs on no FEWER slices needs no witness: from S = 6 on every block has a
+#            window from digit 0.)
+# The entries lie in rows no gather reads -- the gathers read the UNROUNDED operand (fp64 rows, fp32 rows at <= 4 slices), where a
+# quarter would survive: samples without a missing call in any listed SNP (X'B), SNPs without a missing call (X T) -- whose matrix rows
+# count (live, no pin, and not the rows that hold a full operand's maxima).  An entry is used only where fp64 holds the sum exactly (a
+# large entry of a high window and a quarter 56 bits below e_c do not fit).  D3 is left out: its second operand x k / 4 breaks the grid.
+WITNESS_SETS = ("D0", "D1", "D2", "D4")
+WITNESS_ROWS = 3
+
+
+@functools.lru_cache(maxsize=None)
+def witness_rows(name, op, n=N, p=P):
+    codes = genotypes(name, n, p)
+    called = codes != CODE["missing"]
+    nmiss = (~called).sum(axis=1)
+    if op == "x":
+        ok = (nmiss == 0) & live_snps(meansd(name, n, p))
+        pin = PIN_SNP
+    else:  # (SNPs missing in more than a tenth of the samples ride the matrix cores on the hybrid route -- rounded slices -- or are dead)
+        ok = called[nmiss <= n // 10].all(axis=0)
+        pin = PIN_SAMPLE
+    ok[pin:pin + 7] = False
+    rows = np.flatnonzero(ok)[:WITNESS_ROWS]
+    assert rows.size >= 1
+    return rows
+
+
+def witness_operand(name, S_ctx, Sc, b, op, n=N, p=P):
+    """The witness block of a run (an Operand; .witnessed [rows][b] bool: the entries that carry it, rows = witness_rows)."""
+    o = case_operand(name, Sc, b, op, 0, n, p)
+    rows = witness_rows(name, op, n, p)
+    w = Operand()
+    w.__dict__.update(o.__dict__)
+    if Sc < S_ctx:
+        d = np.ldexp(1.0, (o.e - (8 * Sc - 2) - 2).astype(np.int32))[None, :]
+        old = o.x[rows]
+        step = np.where(old > 0, -d, d)  # towards zero: no magnitude grows, the maximum least of all
+        new = old + step
+        w.witnessed = (new - old == step) & (np.abs(new) > 0)  # (exact in fp64, or the entry is left alone)
+        w.x = o.x.copy()
+        w.x[rows] = np.where(w.witnessed, new, old)
+        w.n = None  # (no integer form at Sc: never compared with a reference of its own)
+    else:
+        assert o.pin is not None
+        w.witnessed = np.broadcast_to(o.digit0 >= 1, (rows.size, b)).copy()
+        w.n = 8 * o.n
+        w.n[rows] += w.witnessed
+        w.unit = o.unit - 3
+        w.x = np.ldexp(w.n.astype(np.float64), w.unit[None, :].astype(np.int32))
+        w.x[o.pin], w.x[o.pin + 1] = o.x[o.pin], o.x[o.pin + 1]
+    return w
+
+
+def total_in_units(sl, pin, unit):
+    """Per column: sum over rows (pins apart) and planes of |digit| 256^i 2^(e - F) in units of 2^unit, as Python ints; asserts that every
+    digit's term is a whole number of units (`order_free_total` measured in the operand's own unit, not in that of its lowest plane)."""
+    D = sl.D.astype(np.int64).copy()
+    if pin is not None:
+        D[:, [pin, pin + 1]] = 0
+    S = D.shape[0]
+    tot = []
+    for c in range(D.shape[2]):
+        t = 0
+        for i in range(S):
+            col = D[S - 1 - i, :, c]
+            if not col.any():
+                continue
+            sh = 8 * i + int(sl.e[c]) - sl.F - int(unit[c])  # this plane's weight is 2^sh units
+            if sh < 0:
+                assert not (col & ((1 << -sh) - 1)).any(), (c, i, sh)
+                t += int(np.abs(col).sum()) >> -sh
+            else:
+                t += int(np.abs(col).sum()) << sh
+        tot.append(t)
+    return tot
+
+
+# The chained product, Y = X X' B as the solver runs it (apply_xxt_dev -> xt_i8(chain) -> x_i8(have_max)): the K2 combine leaves the column
+# maxima of the two K3 operands, which are then cut on the pass's slices -- and DO round at 4 and 3 slices.  The reference restates the
+# path instead of tolerating it.  B = integers below 2^CHAIN_BITS = 2^22 times a power of two per column (`chain_block`): K2 is exact at
+# every slice count from 3 (F = 22) and so are the fp32 rows of its gathers, T = X'B in int64.  T / sd and mean T / sd are cut by the slicer's own model at Sc slices with the exponents of their own column
+# maxima; on the list routes the indicator term reads the rows the contract leaves for the gathers -- the unrounded operand, in fp32 at
+# <= 4 slices (24 significant bits) -- and on the hybrid route the dense SNPs' rows are cut on their own.  Y in int64 from those.
+CHAIN_PASSES = (7, 4, 7, 3, 7)
+CHAIN_SETS = ("D0", "D1", "D2", "D4")
+CHAIN_WIDTHS = (16, 32, 64)
+CHAIN_BITS = 22
+CHAIN_S = 7
+
+
+def chain_runs():
+    return [dict(ds=ds, S=CHAIN_S, Sc=Sc, b=b, tiled=None, mode=None, tall=False, q=q)
+            for ds in CHAIN_SETS for q, (Sc, b) in enumerate((Sc, b) for Sc in CHAIN_PASSES for b in CHAIN_WIDTHS)]
+
+
+@functools.lru_cache(maxsize=None)
+def chain_block(name, b, k, n=N, p=P):
+    """Block k (0 / 1) of the chained product's input on data set `name`: .n int64 [n][b], .unit [b], .x = n 2^unit.  Column c leans on
+    one SNP j of the set, n = 3 x 2^20 (g_j - 1) + 20 random bits, so that row j of X'B is about 4 x 3 x 2^20 x (600 homozygotes) > 2^32
+    units while the other rows stay near 2^27: the column maximum then puts the quantum of a 4-slice pass at 8 units, and T / sd, a
+    multiple of 4, rounds.  (With entries below 2^20 the largest |A n| is 4 x 701 x 2^20 < 2^32: nothing could round at 4 slices.)"""
+    rng = np.random.default_rng([b, k, n, 99])
+    codes = genotypes(name, n, p)
+    GM, M = dosage_called(codes)
+    hom = ((GM != 1) & (M == 1)).sum(axis=1) * live_snps(meansd(name, n, p))
+    hom[[PIN_SNP, PIN_SNP + 1]] = 0
+    lean = np.argsort(-hom, kind="stable")[2 * np.arange(b) + k]
+    o = Operand()
+    o.b, o.unit = b, rng.integers(-60, 61, size=b).astype(np.int64)
+    o.n = 3 * 2 ** 20 * ((GM[lean] - 1) * M[lean]).T + rng.integers(-(2 ** 20) + 1, 2 ** 20, size=(n, b), dtype=np.int64)
+    assert np.abs(o.n).max() < 2 ** CHAIN_BITS
+    o.x = np.ldexp(o.n.astype(np.float64), o.unit[None, :].astype(np.int32))
+    o.x.setflags(write=False)
+    return o
+
+
+def hybrid_dense(nmiss, n, S_ctx):
+    """The SNPs whose indicator rows the hybrid route sends to the matrix cores (hybrid_classify)."""
+    return np.asarray(nmiss) > D_CELL * S_ctx / G_CALL * n
+
+
+class ChainModel:
+    """Y [n][b] fp64 and what the exactness bounds need: .T, .units (the unit every term of K3 is a whole multiple of), .ops = the
+    Sliced K3 operands (T / sd, mean T / sd, and the dense SNPs' rows of the latter on the hybrid route), .gathered = per column the sum
+    of |rows the gathers may add| in units, .route."""
+
+
+def _to_units(v, unit):
+    """fp64 -> int64 in units of 2^unit per column, asserted exact."""
+    y = np.ldexp(v, (-unit)[None, :].astype(np.int32))
+    r = np.rint(y)
+    assert np.array_equal(r, y) and np.max(np.abs(r), initial=0) < 2 ** 60
+    return r.astype(np.int64)
+
+
+def _dequant(sl):
+    mf = sl.m.astype(np.float64)
+    assert np.array_equal(mf.astype(np.int64), sl.m)
+    return np.ldexp(mf, (sl.e - sl.F)[None, :].astype(np.int32))
+
+
+def chain_model(name, blk, S_ctx, Sc, n=N, p=P):
+    b = blk.b
+    GM, M = dosage_called(genotypes(name, n, p))
+    E = 1 - M
+    ms = meansd(name, n, p)
+    live = live_snps(ms)
+    nmiss = nmiss_of(name, n, p)
+    c = ChainModel()
+    c.route = pass_route(nmiss, n, S_ctx, Sc, b)
+    # K2, exact: T = (A n) 2^(unit - 2) / sd
+    R = int_matmul(quarter_matrix(name, n, p), blk.n)
+    assert np.max(np.abs(R)) < 2 ** 53
+    T = np.ldexp(R.astype(np.float64), (blk.unit - 2)[None, :].astype(np.int32))
+    c.T = np.where(live[:, None], T / np.where(live, ms[:, 1], 1.0)[:, None], 0.0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        inv = np.where(live, 1.0 / ms[:, 1], 0.0)
+        mu = np.where(live, ms[:, 0] / ms[:, 1], 0.0)
+    slg, slm = Y.Sliced(c.T, p, Sc, Sc * b, rowscale=inv), Y.Sliced(c.T, p, Sc, Sc * b, rowscale=mu)
+    c.ops = [slg, slm]
+    c.units = units = blk.unit  # (binom: sd 1/2, mean 1 -- T / sd = (A n) 2^unit; rounding to slices or to fp32 only coarsens the grid)
+    Xg, Xm = _to_units(_dequant(slg), units), _to_units(_dequant(slm), units)
+    # the rows the gathers read: the unrounded second operand, through fp32 at <= 4 slices
+    rows = slm.x if Sc > 4 else np.ldexp(slm.slice_copy32().astype(np.float64), (slm.e - 1)[None, :].astype(np.int32))
+    Cp = _to_units(rows, units)
+    c.gathered = [0] * b
+    if c.route == 2:
+        assert not E.any()
+        Eterm = 0
+    elif c.route in (0, 1):  # the two-matrix kernels: the indicator meets the digits
+        Eterm = int_matmul(E.T, Xm)
+    else:
+        dense = hybrid_dense(nmiss, n, S_ctx) if c.route == 4 else np.zeros(p, dtype=bool)
+        Eterm = int_matmul(E[~dense].T, Cp[~dense])
+        c.gathered = [int(v) for v in np.abs(Cp[~dense]).sum(axis=0)]
+        if dense.any():  # their rows of mean T / sd, cut on their own with their own column maxima
+            sld = Y.Sliced(np.ascontiguousarray(slm.x[dense]), int(dense.sum()), Sc, Sc * b)
+            c.ops.append(sld)
+            Eterm = Eterm + int_matmul(E[dense].T, _to_units(_dequant(sld), units))
+    Yi = int_matmul(GM.T, Xg) - (Xm.sum(axis=0)[None, :] - Eterm)
+    assert np.max(np.abs(Yi)) < 2 ** 53
+    c.Y = np.ldexp(Yi.astype(np.float64), units[None, :].astype(np.int32))
+    return c
