@@ -8,6 +8,7 @@ from ._lib import LIB_PATH, CLI_PATH, HOOKS_LIB_PATH, HOOKS_CLI_PATH, build, lib
 from .api import Context, flashpca, project, ucca, scca, cv_scca, snp_filter, ld_prune, king_cutoff, qc_filter, count_fam_rows  # noqa: F401
 from .api import king_related, king_classify, write_kin0  # noqa: F401
 from .api import grm, rel_cutoff, write_grm, read_grm  # noqa: F401
+from .api import pcrelate  # noqa: F401
 from .api import debug_synth_host  # noqa: F401
 from .api import check_pca as check  # noqa: F401  (R: check())
 

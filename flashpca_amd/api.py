@@ -432,6 +432,61 @@ class Context:
         check(lib().fpca_bench_grm(self.h, int(reps), _p(ms), C.byref(flops)))
         return ms, flops.value
 
+    # ---- PC-Relate ------------------------------------------------------------------------------------
+    def _pcr_args(self, pcs, train, beta=None):
+        pcs = np.asarray(pcs, dtype=np.float64)
+        if pcs.ndim == 1 and pcs.size == self.N:
+            pcs = pcs.reshape(self.N, 1)
+        if pcs.ndim != 2 or pcs.shape[0] != self.N:
+            raise ValueError("pcs must have one row per sample (%d), it has shape %s" % (self.N, pcs.shape))
+        pcs = np.ascontiguousarray(pcs)
+        if beta is not None:
+            beta = np.ascontiguousarray(beta, dtype=np.float64)
+            if beta.shape != (self.P, pcs.shape[1] + 1):
+                raise ValueError("beta must be %d x %d (one row per SNP, the intercept first), it has shape %s" % (self.P, pcs.shape[1] + 1, beta.shape))
+        return pcs, self._sample_keep(train), beta
+
+    def pcrelate_beta(self, pcs, train=None):
+        """fpca_pcrelate_beta: the P x (npc + 1) coefficients of every SNP's regression on [1 | pcs] over the samples of `train` (a boolean
+        array with one entry per sample, the unrelated set; None: all) -- dosages with the context's mean at a missing call.  pcs: N x npc,
+        npc <= 31.  Half the fitted value is PC-Relate's individual-specific allele frequency."""
+        pcs, t8, _ = self._pcr_args(pcs, train)
+        out = np.empty((self.P, pcs.shape[1] + 1), dtype=np.float64)
+        check(lib().fpca_pcrelate_beta(self.h, _p(pcs), pcs.shape[1], _p(t8), _p(out)))
+        return out
+
+    def pcrelate_block(self, pcs, i0, ni, j0, nj, train=None, eps=0.01, beta=None, den=False):
+        """fpca_pcrelate_block: the ni x nj array of PC-Relate kinship between sample i0 + a and sample j0 + b, any rectangle: with mu =
+        [1 | pcs] beta / 2, the sum of (x_i - 2 mu_i)(x_j - 2 mu_j) over 4 x the sum of sqrt(mu_i (1 - mu_i) mu_j (1 - mu_j)), both over the
+        SNPs that are live, called and have eps < mu < 1 - eps in both samples (NaN when there is none).  beta: what pcrelate_beta returned
+        (None: estimated from `train` inside the call, the same bits).  den=True: (kin, the denominator sums)."""
+        pcs, t8, beta = self._pcr_args(pcs, train, beta)
+        i0, ni, j0, nj = int(i0), int(ni), int(j0), int(nj)
+        if min(i0, ni, j0, nj) < 0:
+            raise ValueError("i0, ni, j0 and nj are non-negative")
+        out = np.empty((max(ni, 1), max(nj, 1)), dtype=np.float64)  # (a zero-sized request still reaches the library's refusal)
+        dn = np.empty(out.shape, dtype=np.float64) if den else None
+        check(lib().fpca_pcrelate_block(self.h, _p(pcs), pcs.shape[1], _p(beta), _p(t8), float(eps), i0, ni, j0, nj, _p(out), _p(dn)))
+        return (out[:ni, :nj], dn[:ni, :nj]) if den else out[:ni, :nj]
+
+    def pcrelate_tri(self, pcs, train=None, eps=0.01, beta=None, den=False):
+        """fpca_pcrelate_tri: the lower triangle of the PC-Relate kinship matrix with its diagonal, row by row -- entry i (i + 1) / 2 + j is
+        kin_ij, j <= i, N (N + 1) / 2 doubles; the diagonal is (1 + inbreeding) / 2.  den=True: (kin, the denominator sums in the same order)."""
+        pcs, t8, beta = self._pcr_args(pcs, train, beta)
+        size = self.N * (self.N + 1) // 2
+        out = np.empty(size, dtype=np.float64)
+        dn = np.empty(size, dtype=np.float64) if den else None
+        check(lib().fpca_pcrelate_tri(self.h, _p(pcs), pcs.shape[1], _p(beta), _p(t8), float(eps), _p(out), _p(dn)))
+        return (out, dn) if den else out
+
+    def bench_pcrelate(self, npc=4, reps=5):
+        """fpca_bench_pcrelate: (milliseconds of each of `reps` passes of PC-Relate's Gram kernel over the whole lower triangle,
+        floating-point operations one pass issues, both Grams counted)."""
+        ms = np.zeros(int(reps), dtype=np.float64)
+        flops = C.c_double(0)
+        check(lib().fpca_bench_pcrelate(self.h, int(npc), int(reps), _p(ms), C.byref(flops)))
+        return ms, flops.value
+
     # ---- genotype census ------------------------------------------------------------------------------
     def snp_counts(self, samples=None):
         """fpca_snp_counts: the P x 4 uint32 array of genotype counts per SNP by raw .bed code (0 homozygous A1, 1 missing, 2 heterozygous,
@@ -1533,6 +1588,32 @@ def grm(prefix, divisor="shared", snps=None, maf=0.0, geno=1.0, ld=None, device=
             with _select_snps(full, prefix, snps, qc, maf, geno, ld)[0] as sub:
                 tri, shared = sub.grm_tri(divisor, counts=True)
     return dict(tri=tri, shared=shared, ids=_fam_ids(prefix))
+
+
+def pcrelate(prefix, pcs, train=None, eps=0.01, snps=None, maf=0.0, geno=1.0, ld=None, device=0):
+    """PC-Relate kinship of a PLINK fileset (Context.pcrelate_tri): a dict with `tri`, the packed lower triangle with the diagonal (entry
+    i (i + 1) / 2 + j, j <= i, over the rows of prefix.fam), `den`, the denominator sums in the same order, `inbreeding` (2 x the diagonal -
+    1), `beta`, the per-SNP coefficients on [1 | pcs] over the selected SNPs, and `ids`, the (FID, IID) pairs.  pcs: one row per sample --
+    flashpca(unrelated=...)["projection_all"][:, :k]; train: the samples the regression is fitted on -- its "unrelated_kept".  snps / maf /
+    geno / ld as in grm(): applied first, over all samples."""
+    qc = not (maf <= 0 and geno >= 1)
+    if ld is not None:
+        ld = _ld_args(ld)
+    N = count_fam_rows(prefix + ".fam")
+
+    def run(ctx):
+        beta = ctx.pcrelate_beta(pcs, train=train)
+        tri, den = ctx.pcrelate_tri(pcs, eps=eps, beta=beta, den=True)
+        return tri, den, beta
+
+    with Context.from_bed(prefix + ".bed", N, device=device, accum="fp64") as full:
+        if snps is None and not qc and ld is None:
+            tri, den, beta = run(full)
+        else:
+            with _select_snps(full, prefix, snps, qc, maf, geno, ld)[0] as sub:
+                tri, den, beta = run(sub)
+    diag = tri[np.arange(N) * (np.arange(N) + 3) // 2]
+    return dict(tri=tri, den=den, inbreeding=2.0 * diag - 1.0, beta=beta, ids=_fam_ids(prefix))
 
 
 def rel_cutoff(prefix, thr=0.025, divisor="shared", snps=None, maf=0.0, geno=1.0, ld=None, keep=None, device=0):

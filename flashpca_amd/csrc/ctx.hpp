@@ -31,6 +31,9 @@
 //                       genotypes on the same sample-major copy -- the sums on the FP64 MFMA with the per-SNP table staged in LDS (k_grm_dot),
 //                       the shared-call counts as one int8 product (k_grm_shared), the divide and the three outputs (k_grm_finish), in slabs
 //                       of rows; king.hip's host rule for the cutoff
+//   pcrelate.hip        fpca_pcrelate_beta / fpca_pcrelate_block / fpca_pcrelate_tri: PC-Relate kinship -- every SNP regressed on [1 | pcs] through
+//                       the K2 pass and a per-SNP Cholesky solve (k_pcr_beta), the operands r = x - 2 mu and w = sqrt(mu (1 - mu)) as dense fp64
+//                       panels (k_pcr_operands), both Grams on the FP64 MFMA from LDS-staged tiles (k_pcr_gram), the divide (k_pcr_finish)
 //   qc_census.hip       fpca_snp_counts / fpca_sample_counts / fpca_hwe_exact / fpca_sample_qc / fpca_snp_qc_samples: genotype counts per SNP
 //                       over chosen samples (k_snp_counts) and per sample over chosen SNPs (k_sample_counts, a column census with vertical
 //                       counters), the HWE exact test (k_hwe_exact, one SNP per lane), the --mind and --geno / --maf / --hwe rules on the host

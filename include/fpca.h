@@ -336,6 +336,49 @@ int fpca_grm_pairs(fpca_ctx *ctx, const uint8_t *keep /* [N] or NULL */, double 
                    double *g, uint32_t *shared /* or NULL */, uint64_t *n_pairs);
 int fpca_grm_cutoff(fpca_ctx *ctx, double thr, int divisor, uint8_t *keep /* [N] in/out */, uint64_t *n_kept);
 
+/* PC-Relate (Conomos et al. 2016): kinship between the samples of the resident matrix adjusted for principal components, on the FP64 matrix
+ * cores -- the second half of the PC-AiR / PC-Relate pipeline, fed by the PCs fpca_pca fits on an unrelated set.  Every SNP is regressed on
+ * the PCs; the fitted value is an individual-specific allele frequency, so that population structure inflates no pair's kinship.
+ *   Dosage    x_is in {2, -, 1, 0} for the raw codes {0, 1, 2, 3}; code 1 is a missing call.
+ *   Live      SNP s is LIVE when sd_s > 1e-9 and neither mean_s nor sd_s is NaN (the rule of the relationship matrix above).  A SNP that is
+ *             not live contributes nowhere and has beta_s = 0.
+ *   V         V = [1 | pcs], N x d, d = npc + 1, 0 <= npc <= 31.  pcs is row-major [N][npc]; the library prepends the ones.
+ *   train     N bytes, or NULL for all samples: the samples whose genotypes estimate beta (the unrelated set).
+ *   beta      beta_s = argmin sum_{i in train} (g_is - V_i beta)^2 with g_is = x_is at a call and mean_s at a missing call.  mean_s is the
+ *             context's own mean over ALL samples (or what fpca_set_meansd loaded): nothing is re-estimated over train.  In steps: B = V with
+ *             the rows outside train zeroed goes through the context's own K2 pass, T_sk = sum_{i in train} z_is V_ik; rhs_sk = mean_s c_k +
+ *             sd_s T_sk with c_k = sum_{i in train} V_ik (sd z = x - mean, whichever standardisation the context has); beta_s = A^-1 rhs_s
+ *             with A = V_train' V_train, factored once on the host by Cholesky in fp64 (A and c summed in long double and rounded once) and
+ *             refused when a pivot is <= 1e-12 x the largest pivot before it; the two substitutions per SNP run on the device.
+ *   Usable    mu_is = V_i.beta_s / 2 (the dot product in the order k = 0 .. d - 1).  SNP s is USABLE in sample i when it is live, called in
+ *             i, and eps < mu_is < 1 - eps (strict).  0 <= eps < 0.5; 0.01 is GENESIS's maf.thresh.
+ *   Operands  r_is = x_is - 2 mu_is and w_is = sqrt(mu_is (1 - mu_is)) where usable, both 0 elsewhere.
+ *      S_ij = sum_s r_is r_js        D_ij = sum_s w_is w_js        kin_ij = S_ij / (4 D_ij)
+ *   one multiply by 4 (exact) and ONE fp64 divide; D_ij == 0 is tested and gives NaN.  The diagonal is (1 + f_i) / 2: the inbreeding
+ *   coefficient is 2 kin_ii - 1.  S and D are accumulated in fp64 without atomics and without a split along the SNPs: a call is
+ *   deterministic, kin_ij and kin_ji are the same bits.
+ *   fpca_pcrelate_beta    beta[P_g][npc + 1], row-major.
+ *   fpca_pcrelate_block   kin[ni][nj], row-major: kin[a][b] is the kinship of samples i0 + a and j0 + b, for any rectangle; den (may be
+ *                         NULL): D likewise.  FPCA_EINVAL when kin would exceed 1 GiB.
+ *   fpca_pcrelate_tri     the lower triangle with the diagonal, row by row: entry i (i + 1) / 2 + j is kin_ij, j <= i, N (N + 1) / 2 entries;
+ *                         den (may be NULL): D in the same order.  Host buffers of any size; computed in slabs of rows, each downloaded as
+ *                         it finishes.
+ *   beta == NULL in the last two means "estimate it from train": the result is bit for bit that of fpca_pcrelate_beta followed by the call
+ *   with its beta.  With beta given, train is ignored.
+ *   Every call makes its own sample-major copy of the packed matrix, a scratch of at most 256 MiB for S and D of a slab and panels of r and
+ *   w of at most 1 GiB (FPCA_ENOMEM with the sizes in the message when one does not fit, or when one 512-SNP panel would pass 1 GiB) and
+ *   frees them before it returns.
+ *   All: FPCA_EINVAL, before any device work, for a NULL context or output, a dense context, a context under a sample mask, one shard of
+ *   several, npc outside 0 .. 31, a non-finite entry of pcs or beta, fewer than npc + 2 training samples, a rank-deficient A, eps outside
+ *   [0, 0.5), and a range outside the context or a zero-sized block.  The context is not changed. */
+int fpca_pcrelate_beta(fpca_ctx *ctx, const double *pcs /* [N][npc] */, int npc, const uint8_t *train /* [N] or NULL */,
+                       double *beta /* [P_g][npc + 1] */);
+int fpca_pcrelate_block(fpca_ctx *ctx, const double *pcs /* [N][npc] */, int npc, const double *beta /* [P_g][npc + 1] or NULL */,
+                        const uint8_t *train /* [N] or NULL */, double eps, uint64_t i0, uint64_t ni, uint64_t j0, uint64_t nj,
+                        double *kin /* [ni][nj] */, double *den /* same, or NULL */);
+int fpca_pcrelate_tri(fpca_ctx *ctx, const double *pcs /* [N][npc] */, int npc, const double *beta /* [P_g][npc + 1] or NULL */,
+                      const uint8_t *train /* [N] or NULL */, double eps, double *kin /* [N (N + 1) / 2] */, double *den /* same, or NULL */);
+
 /* Genotype census: counts per SNP over a chosen set of samples, counts per sample over a chosen set of SNPs, the Hardy-Weinberg exact test
  * on such counts, and the two QC rules on top of them -- PLINK's --mind (per-sample call rate) and --geno / --maf / --hwe over the KEPT
  * samples.  The masks they leave feed fpca_set_sample_mask and fpca_create_snp_subset.

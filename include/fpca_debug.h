@@ -224,6 +224,13 @@ int fpca_bench_king_rel(fpca_ctx *ctx, int reps, double *ms, double *macs);
  * (2 x 32 x 32 x 4 pitch per 32 x 32 block of pairs on or below the diagonal, pad SNPs included).  Test build with FPCA_GRM_BENCH_SHARED=1:
  * the shared-call count kernel (k_grm_shared) is timed instead. */
 int fpca_bench_grm(fpca_ctx *ctx, int reps, double *ms, double *flops);
+/* time the Gram kernel of PC-Relate alone (k_pcr_gram, scripts/pcrelate_measure.py) over the whole lower triangle, slab by slab and panel by
+ * panel as fpca_pcrelate_tri launches it, on a model of npc columns made up here that leaves every call of a live SNP usable: the
+ * sample-major copy, the slab scratch and a panel (the last the untimed pass of both kernels built) are ready before the clock starts;
+ * then `reps` passes with a pair of HIP events around each, ms[reps].  *flops (may be NULL): floating-point operations one pass issues,
+ * both Grams counted (2 x 2 x 32 x 32 x round_up(P_g, 512) per 32 x 32 block of pairs on or below the diagonal).  Test build with
+ * FPCA_PCR_BENCH_OPERANDS=1: the operand kernel (k_pcr_operands), every launch of the triangle, is timed instead. */
+int fpca_bench_pcrelate(fpca_ctx *ctx, int npc, int reps, double *ms, double *flops);
 /* diagnostic (tests): the rules of fpca_sample_qc / fpca_snp_qc_samples on caller arrays, no context and no device involved.  counts:
  * uint32 [N][4] / [P][4] by raw code; n_snps: the SNPs the per-sample counts were taken over; n: the samples the per-SNP counts were taken
  * over; p_hwe[P]: the p-values, read only when min_hwe_p > 0 (may be NULL otherwise); samples[N] / keep[P] in and out.  FPCA_EINVAL for
