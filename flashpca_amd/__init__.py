@@ -9,6 +9,7 @@ from .api import Context, flashpca, project, ucca, scca, cv_scca, snp_filter, ld
 from .api import king_related, king_classify, write_kin0  # noqa: F401
 from .api import grm, rel_cutoff, write_grm, read_grm  # noqa: F401
 from .api import pcrelate  # noqa: F401
+from .api import pcrelate_ibd, pcrelate_related, pcrelate_classify  # noqa: F401
 from .api import debug_synth_host  # noqa: F401
 from .api import check_pca as check  # noqa: F401  (R: check())
 

@@ -142,6 +142,9 @@ SIGNATURES = {
     "fpca_pcrelate_beta": (_I, [_P, _P, _I, _P, _P]),
     "fpca_pcrelate_block": (_I, [_P, _P, _I, _P, _P, _D, _U64, _U64, _U64, _U64, _P, _P]),
     "fpca_pcrelate_tri": (_I, [_P, _P, _I, _P, _P, _D, _P, _P]),
+    "fpca_pcrelate_ibd_block": (_I, [_P, _P, _I, _P, _P, _D, _P, _U64, _U64, _U64, _U64, _P, _P, _P]),
+    "fpca_pcrelate_ibd_tri": (_I, [_P, _P, _I, _P, _P, _D, _P, _P, _P, _P]),
+    "fpca_pcrelate_classify": (_I, [_U64, _P, _P, _P, _P, _D, _D, _P, _P, _P]),
     "fpca_snp_counts": (_I, [_P, _P, _P]),
     "fpca_sample_counts": (_I, [_P, _P, _P]),
     "fpca_hwe_exact": (_I, [_P, _P, _U64, _P]),
@@ -206,6 +209,7 @@ SIGNATURES = {
     "fpca_bench_king_rel": (_I, [_P, _I, _P, C.POINTER(_D)]),
     "fpca_bench_grm": (_I, [_P, _I, _P, C.POINTER(_D)]),
     "fpca_bench_pcrelate": (_I, [_P, _I, _I, _P, C.POINTER(_D)]),
+    "fpca_bench_pcrelate_ibd": (_I, [_P, _I, _I, _P, C.POINTER(_D)]),
     "fpca_debug_sample_qc_rule": (_I, [_P, _U64, _U64, _D, _P, C.POINTER(_U64)]),
     "fpca_debug_snp_qc_counts_rule": (_I, [_P, _P, _U64, _U64, _D, _D, _D, _P, C.POINTER(_U64)]),
     "fpca_bench_qc": (_I, [_P, _I, _P, C.POINTER(_D)]),

@@ -487,6 +487,47 @@ class Context:
         check(lib().fpca_bench_pcrelate(self.h, int(npc), int(reps), _p(ms), C.byref(flops)))
         return ms, flops.value
 
+    def _ibd_f(self, f):
+        if f is None:
+            return None
+        f = np.ascontiguousarray(f, dtype=np.float64)
+        if f.shape != (self.N,):
+            raise ValueError("f must have one entry per sample (%d), it has shape %s" % (self.N, f.shape))
+        return f
+
+    def pcrelate_ibd_block(self, pcs, i0, ni, j0, nj, f=None, train=None, eps=0.01, beta=None):
+        """fpca_pcrelate_ibd_block: PC-Relate's IBD sharing between sample i0 + a and sample j0 + b, any rectangle -- a dict of ni x nj arrays:
+        `k2` = sum q_i q_j / sum v_i v_j - f_i f_j, `k0` = the opposite homozygotes over sum (mu_i^2 (1 - mu_j)^2 + (1 - mu_i)^2 mu_j^2), both
+        over the SNPs usable in both samples (NaN when there is none), and `nsnp`, their number (uint32).  f: the inbreeding coefficients,
+        2 x the diagonal of pcrelate_tri - 1 (None: zeros).  pcs, train, eps, beta as in pcrelate_block."""
+        pcs, t8, beta = self._pcr_args(pcs, train, beta)
+        f = self._ibd_f(f)
+        i0, ni, j0, nj = int(i0), int(ni), int(j0), int(nj)
+        if min(i0, ni, j0, nj) < 0:
+            raise ValueError("i0, ni, j0 and nj are non-negative")
+        shape = (max(ni, 1), max(nj, 1))  # (a zero-sized request still reaches the library's refusal)
+        k2, k0, n = np.empty(shape, dtype=np.float64), np.empty(shape, dtype=np.float64), np.empty(shape, dtype=np.uint32)
+        check(lib().fpca_pcrelate_ibd_block(self.h, _p(pcs), pcs.shape[1], _p(beta), _p(t8), float(eps), _p(f), i0, ni, j0, nj, _p(k2), _p(k0), _p(n)))
+        return dict(k2=k2[:ni, :nj], k0=k0[:ni, :nj], nsnp=n[:ni, :nj])
+
+    def pcrelate_ibd_tri(self, pcs, f=None, train=None, eps=0.01, beta=None):
+        """fpca_pcrelate_ibd_tri: what pcrelate_ibd_block returns for the lower triangle with its diagonal, row by row -- entry
+        i (i + 1) / 2 + j, j <= i, N (N + 1) / 2 entries in each of `k2`, `k0`, `nsnp`.  The diagonal carries no meaning."""
+        pcs, t8, beta = self._pcr_args(pcs, train, beta)
+        f = self._ibd_f(f)
+        size = self.N * (self.N + 1) // 2
+        k2, k0, n = np.empty(size, dtype=np.float64), np.empty(size, dtype=np.float64), np.empty(size, dtype=np.uint32)
+        check(lib().fpca_pcrelate_ibd_tri(self.h, _p(pcs), pcs.shape[1], _p(beta), _p(t8), float(eps), _p(f), _p(k2), _p(k0), _p(n)))
+        return dict(k2=k2, k0=k0, nsnp=n)
+
+    def bench_pcrelate_ibd(self, npc=4, reps=5):
+        """fpca_bench_pcrelate_ibd: (milliseconds of each of `reps` passes of the three Gram instances of PC-Relate's IBD sharing over the
+        whole lower triangle, floating-point operations one pass issues, seven products counted)."""
+        ms = np.zeros(int(reps), dtype=np.float64)
+        flops = C.c_double(0)
+        check(lib().fpca_bench_pcrelate_ibd(self.h, int(npc), int(reps), _p(ms), C.byref(flops)))
+        return ms, flops.value
+
     # ---- genotype census ------------------------------------------------------------------------------
     def snp_counts(self, samples=None):
         """fpca_snp_counts: the P x 4 uint32 array of genotype counts per SNP by raw .bed code (0 homozygous A1, 1 missing, 2 heterozygous,
@@ -1614,6 +1655,69 @@ def pcrelate(prefix, pcs, train=None, eps=0.01, snps=None, maf=0.0, geno=1.0, ld
                 tri, den, beta = run(sub)
     diag = tri[np.arange(N) * (np.arange(N) + 3) // 2]
     return dict(tri=tri, den=den, inbreeding=2.0 * diag - 1.0, beta=beta, ids=_fam_ids(prefix))
+
+
+def pcrelate_classify(kin, k0, k2, nsnp, k0_switch=2 ** -5.5, po_k0=0.1):
+    """fpca_pcrelate_classify (host only): (k0_out, k1_out, type) of every pair from its PC-Relate kinship, the IBS0 form of k0, k2 and the
+    shared-SNP count: k0_out = k0 where kin > k0_switch, else 1 - 4 kin + k2; k1_out = 1 - k0_out - k2; type: king_classify's codes at KING's
+    cut points on kin, parent-offspring (1) apart from full sibs (2) by k0_out < po_k0.  Both thresholds are conventions."""
+    kin = np.ascontiguousarray(kin, dtype=np.float64)
+    k0 = np.ascontiguousarray(k0, dtype=np.float64)
+    k2 = np.ascontiguousarray(k2, dtype=np.float64)
+    nsnp = np.ascontiguousarray(nsnp, dtype=np.uint32)
+    if kin.ndim != 1 or not (k0.shape == k2.shape == nsnp.shape == kin.shape):
+        raise ValueError("kin, k0, k2 and nsnp have one entry per pair; they have shapes %s, %s, %s and %s" % (kin.shape, k0.shape, k2.shape, nsnp.shape))
+    k0_out, k1_out, typ = np.empty(kin.size), np.empty(kin.size), np.empty(kin.size, dtype=np.uint8)
+    check(lib().fpca_pcrelate_classify(kin.size, _p(kin), _p(k0), _p(k2), _p(nsnp), float(k0_switch), float(po_k0), _p(k0_out), _p(k1_out), _p(typ)))
+    return k0_out, k1_out, typ
+
+
+def pcrelate_ibd(prefix, pcs, train=None, eps=0.01, k0_switch=2 ** -5.5, snps=None, maf=0.0, geno=1.0, ld=None, device=0):
+    """PC-Relate kinship and IBD sharing of a PLINK fileset: what pcrelate() returns (`tri`, `den`, `inbreeding`, `beta`, `ids`) and the
+    packed lower triangles `k0`, `k1`, `k2` (the probabilities of sharing 0, 1, 2 alleles identical by descent) and `nsnp` (the SNPs usable
+    in both samples), entry i (i + 1) / 2 + j.  beta is estimated once; f of the k2 correction is `inbreeding`; k0 is the IBS0 form where
+    the kinship is above k0_switch and 1 - 4 kin + k2 elsewhere (pcrelate_classify).  The diagonal of the four carries no meaning."""
+    qc = not (maf <= 0 and geno >= 1)
+    if ld is not None:
+        ld = _ld_args(ld)
+    N = count_fam_rows(prefix + ".fam")
+
+    def run(ctx):
+        beta = ctx.pcrelate_beta(pcs, train=train)
+        tri, den = ctx.pcrelate_tri(pcs, eps=eps, beta=beta, den=True)
+        f = 2.0 * tri[np.arange(N) * (np.arange(N) + 3) // 2] - 1.0
+        # (a sample without a usable SNP has a NaN diagonal; its k2 is NaN whatever f is, and the library refuses a non-finite f)
+        return tri, den, beta, f, ctx.pcrelate_ibd_tri(pcs, f=np.nan_to_num(f), eps=eps, beta=beta)
+
+    with Context.from_bed(prefix + ".bed", N, device=device, accum="fp64") as full:
+        if snps is None and not qc and ld is None:
+            tri, den, beta, f, ibd = run(full)
+        else:
+            with _select_snps(full, prefix, snps, qc, maf, geno, ld)[0] as sub:
+                tri, den, beta, f, ibd = run(sub)
+    k0, k1, _ = pcrelate_classify(tri, ibd["k0"], ibd["k2"], ibd["nsnp"], k0_switch=k0_switch)
+    return dict(tri=tri, den=den, inbreeding=f, beta=beta, ids=_fam_ids(prefix), k0=k0, k1=k1, k2=ibd["k2"], nsnp=ibd["nsnp"])
+
+
+def pcrelate_related(prefix, pcs, train=None, thr=2 ** -5.5, min_snps=0, po_k0=0.1, eps=0.01, k0_switch=2 ** -5.5, snps=None, maf=0.0, geno=1.0,
+                     ld=None, device=0):
+    """The PC-Relate relationship table of a PLINK fileset: every pair of rows i < j of prefix.fam with PC-Relate kinship above thr (2^-5.5:
+    third degree and closer) and at least min_snps SNPs usable in both, sorted by (i, j) -- a dict of the columns `i`, `j`, `kin`, `k0`,
+    `k1`, `k2`, `nsnp`, `type` (pcrelate_classify: parent-offspring apart from full sibs by k0 < po_k0).  Built on the host from
+    pcrelate_ibd()'s triangles; the other arguments are its."""
+    r = pcrelate_ibd(prefix, pcs, train=train, eps=eps, k0_switch=k0_switch, snps=snps, maf=maf, geno=geno, ld=ld, device=device)
+    N = len(r["inbreeding"])
+    i, j = np.tril_indices(N, -1)  # (row-major over the strict lower triangle: sorted by (larger, smaller))
+    at = i * (i + 1) // 2 + j
+    with np.errstate(invalid="ignore"):
+        sel = (r["tri"][at] > thr) & (r["nsnp"][at] >= min_snps)
+    lo, hi, at = j[sel].astype(np.uint32), i[sel].astype(np.uint32), at[sel]
+    order = np.lexsort((hi, lo))
+    lo, hi, at = lo[order], hi[order], at[order]
+    kin, k2, nsnp = r["tri"][at], r["k2"][at], r["nsnp"][at]
+    # (k0 of the triangle is already the chosen estimator: a switch below every kinship hands it through)
+    k0, k1, typ = pcrelate_classify(kin, r["k0"][at], k2, nsnp, k0_switch=-np.finfo(np.float64).max, po_k0=po_k0)
+    return dict(i=lo, j=hi, kin=kin, k0=k0, k1=k1, k2=k2, nsnp=nsnp, type=typ)
 
 
 def rel_cutoff(prefix, thr=0.025, divisor="shared", snps=None, maf=0.0, geno=1.0, ld=None, keep=None, device=0):

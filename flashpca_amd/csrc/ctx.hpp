@@ -34,6 +34,10 @@
 //   pcrelate.hip        fpca_pcrelate_beta / fpca_pcrelate_block / fpca_pcrelate_tri: PC-Relate kinship -- every SNP regressed on [1 | pcs] through
 //                       the K2 pass and a per-SNP Cholesky solve (k_pcr_beta), the operands r = x - 2 mu and w = sqrt(mu (1 - mu)) as dense fp64
 //                       panels (k_pcr_operands), both Grams on the FP64 MFMA from LDS-staged tiles (k_pcr_gram), the divide (k_pcr_finish)
+//   pcrelate_ibd.hip    fpca_pcrelate_ibd_block / fpca_pcrelate_ibd_tri / fpca_pcrelate_classify: PC-Relate's IBD sharing -- k2, k0 and the shared-SNP
+//                       count from seven products over three operand panels (k_pcr_ibd_operands; k_pcr_ibd, three instances of one template
+//                       with k_pcr_gram's geometry), the divides and the f_i f_j correction (k_pcr_ibd_finish), the estimator rule and the
+//                       relationship type on the host (+ pcrelate.hpp, the host side it shares with pcrelate.hip)
 //   qc_census.hip       fpca_snp_counts / fpca_sample_counts / fpca_hwe_exact / fpca_sample_qc / fpca_snp_qc_samples: genotype counts per SNP
 //                       over chosen samples (k_snp_counts) and per sample over chosen SNPs (k_sample_counts, a column census with vertical
 //                       counters), the HWE exact test (k_hwe_exact, one SNP per lane), the --mind and --geno / --maf / --hwe rules on the host

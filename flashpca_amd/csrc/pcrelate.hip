@@ -29,25 +29,12 @@
 
 #include "ctx.hpp"
 #include "launch_check.hpp"
+#include "pcrelate.hpp"
 #include "../../include/fpca_debug.h"
 
 using namespace fpca;
 
 namespace {
-
-constexpr int PCR_TILE = 64;                         // samples per workgroup tile side (2 waves x 32)
-constexpr int PCR_STEP = 16;                         // SNPs of one LDS step
-constexpr int PCR_CHUNK = 512;                       // panels are whole chunks of this many SNPs
-constexpr int PCR_MAXD = 32;                         // columns of V: 1 + npc
-constexpr int PCR_BLK_SNPS = 64;                     // SNPs (and samples) of one workgroup of k_pcr_operands
-constexpr uint64_t PCR_BLOCK_LIMIT = 1ull << 30;     // bytes of an fpca_pcrelate_block buffer
-constexpr uint64_t PCR_LAUNCH_PAIRS = 1ull << 18;    // tile pairs of one launch
-constexpr uint64_t PCR_SLAB_BYTES = 1ull << 28;      // S and D of one slab
-constexpr uint64_t PCR_PANEL_BYTES = 1ull << 30;     // r and w of one panel
-constexpr int PCR_RECT = 0, PCR_TRI = 1;
-
-typedef double d4 __attribute__((ext_vector_type(4)));
-typedef double d2 __attribute__((ext_vector_type(2)));
 
 // lc: L [32][32] row-major (the lower triangle; what lies at or past d is the identity's and is not read), then c [32].  One lane per SNP; a
 // lane's right-hand side lives in its own LDS column, so the loops over d index no register array.
@@ -254,7 +241,11 @@ __global__ __launch_bounds__(256) void k_pcr_finish(const double *__restrict__ S
    if (den) den[o] = dd;
 }
 
-// ---- host ---------------------------------------------------------------------------------------------------------------
+} // namespace
+
+// ---- host: what pcrelate_ibd.hip shares is declared in pcrelate.hpp ------------------------------------------------------
+
+namespace fpca {
 
 void pcr_refuse(const fpca_ctx *c, const char *fn)
 {
@@ -353,34 +344,28 @@ void pcr_beta_dev(fpca_ctx *c, const char *fn, const std::vector<double> &V, int
    HIP_CHECK(hipStreamSynchronize(s)); // (B and lc are the host's)
 }
 
-uint64_t pcr_env(const char *name, uint64_t unit)
+uint64_t pcr_env(const char *v, uint64_t unit)
 {
-   const char *v = FPCA_TEST_ENV(name);
    if (!v || std::atoll(v) <= 0) return 0;
    return round_up((uint64_t)std::atoll(v), unit);
 }
 
 // rows of a slab whose cells are `cols` wide: S and D within PCR_SLAB_BYTES, the tile pairs within one launch; whole tiles, at least one
+} // namespace fpca
+
+namespace {
+
 uint64_t pcr_slab_rows(uint64_t cols)
 {
-   if (const uint64_t forced = pcr_env("FPCA_PCR_SLAB_ROWS", PCR_TILE)) return forced;
+   if (const uint64_t forced = PCR_ENV("FPCA_PCR_SLAB_ROWS", PCR_TILE)) return forced;
    const uint64_t by_mem = PCR_SLAB_BYTES / (cols * 2 * sizeof(double)) / PCR_TILE;
    const uint64_t by_launch = PCR_LAUNCH_PAIRS / ((cols + PCR_TILE - 1) / PCR_TILE);
    return std::min<uint64_t>(std::max<uint64_t>(std::min(by_mem, by_launch), 1), 512) * PCR_TILE; // (a row is one grid.y of k_pcr_finish)
 }
 
-// device buffers of one call
-struct PcrBufs {
-   DevMem<uint8_t> d_smp; // the sample-major copy [N_pad][pitch]
-   size_t pitch = 0;
-   DevMem<double> d_V, d_beta; // [N][d], [P_g][d]
-   DevMem<d2> d_panel;
-   uint64_t panel_snps = 0, panel_rows = 0; // SNPs of a panel; the rows it has room for
-   DevMem<double> d_S, d_D, d_kin, d_den;   // the slab: sums [rows][ld], outputs
-   size_t ld = 0;
-   int d = 0;
-   double lo = 0, hi = 0;
-};
+} // namespace
+
+namespace fpca {
 
 // the sample-major copy, V and (given) beta on the device
 void pcr_make_operand(fpca_ctx *c, PcrBufs &s, const char *fn, const std::vector<double> &V, int d, const double *beta)
@@ -400,11 +385,15 @@ void pcr_make_operand(fpca_ctx *c, PcrBufs &s, const char *fn, const std::vector
    if (beta) HIP_CHECK(hipMemcpyAsync(s.d_beta.p, beta, (size_t)c->P_g * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
 }
 
+} // namespace fpca
+
+namespace {
+
 // the panel for slabs that need up to `rows` panel rows: as many whole chunks as PCR_PANEL_BYTES holds, at least one
 void pcr_alloc_panel(const fpca_ctx *c, PcrBufs &s, uint64_t rows, const char *fn)
 {
    const uint64_t slots = round_up(c->P_g, PCR_CHUNK);
-   uint64_t snps = pcr_env("FPCA_PCR_PANEL_SNPS", PCR_CHUNK);
+   uint64_t snps = PCR_ENV("FPCA_PCR_PANEL_SNPS", PCR_CHUNK);
    if (!snps) snps = PCR_PANEL_BYTES / (rows * sizeof(d2)) / PCR_CHUNK * PCR_CHUNK;
    if (!snps)
       throw Error(FPCA_ENOMEM, std::string(fn) + ": one panel of " + std::to_string(PCR_CHUNK) + " SNPs x " + std::to_string(rows) + " samples needs " +
@@ -429,11 +418,9 @@ void pcr_alloc_slab(const fpca_ctx *c, PcrBufs &s, uint64_t rows, uint64_t cols,
    if (out && den) s.d_den = DevMem<double>(cells, fn, "slab scratch (output denominators)", 0, detail, c->device);
 }
 
-// how the samples of a slab map to panel rows: the row tiles [i0, i0 + 64 nti) and the column tiles [j0, j0 + 64 ntj) as one run of rows
-// where they overlap or touch, else one after the other
-struct PcrMap {
-   uint64_t s0, n0, s1, rows, pa0, pb0;
-};
+} // namespace
+
+namespace fpca {
 
 PcrMap pcr_map(uint64_t i0, uint64_t iend, uint64_t j0, uint64_t jend)
 {
@@ -444,6 +431,10 @@ PcrMap pcr_map(uint64_t i0, uint64_t iend, uint64_t j0, uint64_t jend)
    }
    return {i0, ea - i0, j0, (ea - i0) + (eb - j0), 0, ea - i0};
 }
+
+} // namespace fpca
+
+namespace {
 
 // S and D of the cells [i0, iend) x [j0, jend) into the slab scratch: per panel, the operands, then the Gram.  what: 3 both kernels, 1 the
 // operand kernel alone, 2 the Gram alone (on whatever the panel holds: the bench hook)

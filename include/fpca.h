@@ -379,6 +379,62 @@ int fpca_pcrelate_block(fpca_ctx *ctx, const double *pcs /* [N][npc] */, int npc
 int fpca_pcrelate_tri(fpca_ctx *ctx, const double *pcs /* [N][npc] */, int npc, const double *beta /* [P_g][npc + 1] or NULL */,
                       const uint8_t *train /* [N] or NULL */, double eps, double *kin /* [N (N + 1) / 2] */, double *den /* same, or NULL */);
 
+/* PC-Relate IBD sharing: the probabilities k0, k1, k2 that a pair shares 0, 1, 2 alleles identical by descent, adjusted for the principal
+ * components as the kinship above is, the SNPs usable in both samples, and the relationship type they imply -- what tells a parent-offspring
+ * pair (k0 = 0) from full sibs (k0 = 1/4) where both have kinship 1/4.  Dosage, live SNPs, V = [1 | pcs], beta, mu_is = V_i.beta_s / 2 (the dot
+ * product in the order k = 0 .. d - 1) and USABLE (live, called, eps < mu_is < 1 - eps, strict) are those of PC-Relate above, unchanged.
+ *   Operands  m_is in {0, 1} is the usable indicator.  At a usable cell, with mu = mu_is and x = x_is:
+ *                v = mu (1 - mu)        gD = mu if x = 0, 0 if x = 1, 1 - mu if x = 2        q = gD - v
+ *                u = mu^2               t = (1 - mu)^2               a = [x = 0]               c = [x = 2]
+ *             each product and each difference rounded once (nothing is fused); every operand is 0 where m_is = 0.
+ *   Sums      Q_ij = sum_s q_is q_js        E_ij = sum_s v_is v_js        H_ij = sum_s (u_is t_js + t_is u_js)
+ *             I0_ij = sum_s (a_is c_js + c_is a_js), the opposite homozygotes among the SNPs usable in both samples
+ *             n_ij = sum_s m_is m_js
+ *             all in fp64 without atomics and without a split along the SNPs: a call is deterministic.  The two halves of H, sum u_i t_j and
+ *             sum t_i u_j, are kept apart in SNP order and added once, so k2, k0 and nsnp of (i, j) and (j, i) are the same bits.  I0 and n
+ *             are integers, exact.
+ *   k2_ij   = Q_ij / E_ij - f_i f_j (the corrected form of GENESIS): ONE fp64 divide, one rounded multiply, one rounded subtract, never a
+ *             fused multiply-add; E_ij == 0 is tested and gives NaN.  f[N] are inbreeding coefficients supplied by the caller -- 2 kin_ii - 1
+ *             from fpca_pcrelate_tri; NULL means zeros.
+ *   k0_ij   = I0_ij / H_ij: one divide; H_ij == 0 is tested and gives NaN.
+ *   nsnp_ij = n_ij as uint32.
+ *   Diagonal entries follow the same formulas and carry no meaning.
+ *   fpca_pcrelate_ibd_block   k2[ni][nj], k0[ni][nj], nsnp[ni][nj], row-major, of samples i0 + a and j0 + b, for any rectangle.  Any of the
+ *                             three may be NULL, not all three.  FPCA_EINVAL when ni x nj doubles would exceed 1 GiB.
+ *   fpca_pcrelate_ibd_tri     the lower triangle with the diagonal, row by row: entry i (i + 1) / 2 + j, j <= i, N (N + 1) / 2 entries each;
+ *                             host buffers of any size, computed in slabs of rows, each downloaded as it finishes.
+ *   beta == NULL means "estimate it from train", bit for bit that of fpca_pcrelate_beta followed by the call with its beta.
+ *   Every call makes its own sample-major copy of the packed matrix, a scratch of at most 256 MiB for the six sums of a slab (Q, E, the two
+ *   halves of H, 2 I0, n) and three operand panels of at most 1 GiB together (FPCA_ENOMEM with the sizes in the message when one does not fit,
+ *   or when three 512-SNP panels would pass 1 GiB) and frees them before it returns.
+ *   Both: FPCA_EINVAL, before any device work, for everything fpca_pcrelate_block refuses -- a NULL context, a dense context, a context under
+ *   a sample mask, one shard of several, npc outside 0 .. 31, a non-finite entry of pcs or beta, fewer than npc + 2 training samples, a
+ *   rank-deficient A, eps outside [0, 0.5), a range outside the context or a zero-sized block -- for three NULL outputs and for a non-finite
+ *   entry of f.  The context is not changed.
+ *   fpca_pcrelate_classify    host only, no context: per pair p from kin[p] (fpca_pcrelate_tri), k0[p] (the IBS0 form above), k2[p], nsnp[p]
+ *                                k0_out = k0 when kin > k0_switch, else 1 - 4 kin + k2 (the paper's rule: the IBS0 form for close pairs)
+ *                                k1_out = 1 - k0_out - k2
+ *                             and type[p], fpca_king_classify's codes at KING's cut points on kin, in this order:
+ *                                255  no value: kin is NaN, k0_out is NaN or nsnp == 0
+ *                                  5  duplicate / MZ twin: kin > 0.354
+ *                                  1  parent-offspring: 0.177 < kin <= 0.354 and k0_out < po_k0
+ *                                  2  full sibs: 0.177 < kin <= 0.354 otherwise
+ *                                  3  second degree: 0.0884 < kin <= 0.177
+ *                                  4  third degree: 0.0442 < kin <= 0.0884
+ *                                  0  unrelated
+ *                             FPCA_EINVAL for a NULL array with n_pairs > 0 and for a k0_switch or po_k0 that is NaN or infinite.  Both
+ *                             thresholds are conventions of the caller: the Python layer passes k0_switch = 2^-5.5 (the paper's third-degree
+ *                             bound) and po_k0 = 0.1 (after KING's manual).  Parity with GENESIS::pcrelate is not claimed. */
+int fpca_pcrelate_ibd_block(fpca_ctx *ctx, const double *pcs /* [N][npc] */, int npc, const double *beta /* [P_g][npc + 1] or NULL */,
+                            const uint8_t *train /* [N] or NULL */, double eps, const double *f /* [N] or NULL */, uint64_t i0, uint64_t ni,
+                            uint64_t j0, uint64_t nj, double *k2 /* [ni][nj] or NULL */, double *k0 /* same, or NULL */,
+                            uint32_t *nsnp /* same, or NULL */);
+int fpca_pcrelate_ibd_tri(fpca_ctx *ctx, const double *pcs /* [N][npc] */, int npc, const double *beta /* [P_g][npc + 1] or NULL */,
+                          const uint8_t *train /* [N] or NULL */, double eps, const double *f /* [N] or NULL */,
+                          double *k2 /* [N (N + 1) / 2] or NULL */, double *k0 /* same, or NULL */, uint32_t *nsnp /* same, or NULL */);
+int fpca_pcrelate_classify(uint64_t n_pairs, const double *kin, const double *k0, const double *k2, const uint32_t *nsnp, double k0_switch,
+                           double po_k0, double *k0_out /* [n_pairs] */, double *k1_out /* [n_pairs] */, uint8_t *type /* [n_pairs] */);
+
 /* Genotype census: counts per SNP over a chosen set of samples, counts per sample over a chosen set of SNPs, the Hardy-Weinberg exact test
  * on such counts, and the two QC rules on top of them -- PLINK's --mind (per-sample call rate) and --geno / --maf / --hwe over the KEPT
  * samples.  The masks they leave feed fpca_set_sample_mask and fpca_create_snp_subset.

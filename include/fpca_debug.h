@@ -231,6 +231,12 @@ int fpca_bench_grm(fpca_ctx *ctx, int reps, double *ms, double *flops);
  * both Grams counted (2 x 2 x 32 x 32 x round_up(P_g, 512) per 32 x 32 block of pairs on or below the diagonal).  Test build with
  * FPCA_PCR_BENCH_OPERANDS=1: the operand kernel (k_pcr_operands), every launch of the triangle, is timed instead. */
 int fpca_bench_pcrelate(fpca_ctx *ctx, int npc, int reps, double *ms, double *flops);
+/* fpca_bench_pcrelate for PC-Relate's IBD sharing (scripts/pcrelate_ibd_measure.py): the three instances of k_pcr_ibd alone over the whole
+ * lower triangle, slab by slab and panel by panel as fpca_pcrelate_ibd_tri launches them, on the same made-up model; the sample-major copy,
+ * the slab scratch and the three panels (the last the untimed pass of all kernels built) are ready before the clock starts.  *flops (may be
+ * NULL): seven products counted (7 x 2 x 32 x 32 x round_up(P_g, 512) per 32 x 32 block of pairs on or below the diagonal).  Test build
+ * with FPCA_PCR_BENCH_OPERANDS=1: the operand kernel (k_pcr_ibd_operands), every launch of the triangle, is timed instead. */
+int fpca_bench_pcrelate_ibd(fpca_ctx *ctx, int npc, int reps, double *ms, double *flops);
 /* diagnostic (tests): the rules of fpca_sample_qc / fpca_snp_qc_samples on caller arrays, no context and no device involved.  counts:
  * uint32 [N][4] / [P][4] by raw code; n_snps: the SNPs the per-sample counts were taken over; n: the samples the per-SNP counts were taken
  * over; p_hwe[P]: the p-values, read only when min_hwe_p > 0 (may be NULL otherwise); samples[N] / keep[P] in and out.  FPCA_EINVAL for
