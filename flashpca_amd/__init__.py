@@ -10,6 +10,7 @@ from .api import king_related, king_classify, write_kin0  # noqa: F401
 from .api import grm, rel_cutoff, write_grm, read_grm  # noqa: F401
 from .api import pcrelate  # noqa: F401
 from .api import pcrelate_ibd, pcrelate_related, pcrelate_classify  # noqa: F401
+from .api import pcair, pcair_partition, pcair_partition_rule  # noqa: F401
 from .api import debug_synth_host  # noqa: F401
 from .api import check_pca as check  # noqa: F401  (R: check())
 

@@ -135,6 +135,10 @@ SIGNATURES = {
     "fpca_king_related": (_I, [_P, _P, _D, C.c_uint32, _U64, _P, _P, _P, _P, C.POINTER(_U64)]),
     "fpca_king_cutoff_shared": (_I, [_P, _D, C.c_uint32, _P, C.POINTER(_U64)]),
     "fpca_king_classify": (_I, [_U64, _P, _P, _D, _P]),
+    "fpca_king_census": (_I, [_P, _P, _D, _D, _P, _P, _U64, _P, _P]),
+    "fpca_pcair_partition": (_I, [_U64, _U64, _P, _P, _P, _P, _P, C.POINTER(_U64)]),
+    "fpca_pcair_king": (_I, [_P, _D, _D, _P, C.POINTER(_U64), _P, _P]),
+    "fpca_pcair_pairs": (_I, [_P, _D, _U64, _P, _P, _P, _P, C.POINTER(_U64), _P]),
     "fpca_grm_block": (_I, [_P, _U64, _U64, _U64, _U64, _I, _P, _P]),
     "fpca_grm_tri": (_I, [_P, _I, _P, _P]),
     "fpca_grm_pairs": (_I, [_P, _P, _D, _I, _U64, _P, _P, _P, _P, C.POINTER(_U64)]),
@@ -207,6 +211,7 @@ SIGNATURES = {
     "fpca_debug_king_rule": (_I, [_P, _P, _U64, _U64, _P, C.POINTER(_U64)]),
     "fpca_bench_king": (_I, [_P, _I, _P, C.POINTER(_D)]),
     "fpca_bench_king_rel": (_I, [_P, _I, _P, C.POINTER(_D)]),
+    "fpca_bench_king_census": (_I, [_P, _I, _P]),
     "fpca_bench_grm": (_I, [_P, _I, _P, C.POINTER(_D)]),
     "fpca_bench_pcrelate": (_I, [_P, _I, _I, _P, C.POINTER(_D)]),
     "fpca_bench_pcrelate_ibd": (_I, [_P, _I, _I, _P, C.POINTER(_D)]),

@@ -48,6 +48,42 @@ def _snp_mask(snps, P):
     return mask
 
 
+def _pair_indices(pairs, name):
+    """(i, j) as two contiguous uint32 arrays of one length from a pair of index arrays (None: two empty ones); the library checks them
+    against N."""
+    if pairs is None:
+        return np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint32)
+    try:
+        i, j = pairs
+    except (TypeError, ValueError):
+        raise ValueError("%s is (i, j): two arrays of sample indices" % name)
+    out = []
+    for a in (i, j):
+        a = np.asarray(a)
+        if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+            raise ValueError("%s holds one-dimensional arrays of integer sample indices" % name)
+        a = a.astype(np.int64)
+        if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+            raise ValueError("%s holds sample indices between 0 and 2^32 - 1" % name)
+        out.append(np.ascontiguousarray(a, dtype=np.uint32))
+    if out[0].shape != out[1].shape:
+        raise ValueError("%s: i and j have one entry per pair; they have shapes %s and %s" % (name, out[0].shape, out[1].shape))
+    return out[0], out[1]
+
+
+def _kin_pairs(kin_pairs):
+    """(i, j, kin) of PC-AiR's outside relatives as contiguous uint32 / uint32 / float64 arrays of one length."""
+    try:
+        i, j, kin = kin_pairs
+    except (TypeError, ValueError):
+        raise ValueError("kin_pairs is (i, j, kin): two arrays of sample indices and the kinship of each pair")
+    i, j = _pair_indices((i, j), "kin_pairs")
+    kin = np.ascontiguousarray(kin, dtype=np.float64)
+    if kin.shape != i.shape:
+        raise ValueError("kin_pairs: kin has one entry per pair (%d), it has shape %s" % (i.size, kin.shape))
+    return i, j, kin
+
+
 def _synth_model(n_pop, fst, missing_rate, realistic, maf_model, missing_model, conc_frac, lognormal_sigma):
     return _lib.SynthModel(n_pop, fst, missing_rate, int(realistic if maf_model is None else maf_model),
                            int(realistic if missing_model is None else missing_model), conc_frac, lognormal_sigma)
@@ -370,6 +406,51 @@ class Context:
         macs = C.c_double(0)
         check(lib().fpca_bench_king_rel(self.h, int(reps), _p(ms), C.byref(macs)))
         return ms, macs.value
+
+    # ---- PC-AiR's partition ---------------------------------------------------------------------------
+    def king_census(self, kin_thr=2 ** -5.5, div_thr=-2 ** -5.5, keep=None, exclude=None):
+        """fpca_king_census: (n_rel, n_div), two uint32 arrays with one entry per sample -- the number of pairs with the sample whose
+        KING-robust kinship phi is above kin_thr (related) and the number whose phi is below div_thr, that are not related, and that are
+        not listed in `exclude` (divergent in ancestry), both among the samples of `keep` (None: all; a sample outside counts 0).
+        exclude: (i, j), two arrays of sample indices -- pairs in either order, repeats allowed.  One pass over the triangle; a NaN phi is
+        neither; kin_thr may be +inf."""
+        k8 = self._sample_keep(keep)
+        ei, ej = _pair_indices(exclude, "exclude")
+        n_rel = np.zeros(self.N, dtype=np.uint32)
+        n_div = np.zeros(self.N, dtype=np.uint32)
+        check(lib().fpca_king_census(self.h, _p(k8), float(kin_thr), float(div_thr), _p(ei), _p(ej), ei.size, _p(n_rel), _p(n_div)))
+        return n_rel, n_div
+
+    def pcair_partition(self, kin_thr=2 ** -5.5, div_thr=-2 ** -5.5, keep=None, kin_pairs=None, counts=False):
+        """fpca_pcair_king / fpca_pcair_pairs: PC-AiR's unrelated set as a boolean mask over the samples -- among those of `keep` (None:
+        all), one sample at a time goes until no related pair remains: the one in most related pairs; among equals the one in fewest
+        divergent pairs (king_census's n_div, fixed); among equals the one whose kinship to its remaining relatives sums lowest; among
+        equals the largest index.  Related pairs are those with KING-robust phi > kin_thr, from one fused pass with the census; or, with
+        kin_pairs=(i, j, kin), exactly the listed pairs (PC-Relate's, the relationship matrix's) -- KING then only counts the divergent
+        pairs, never one of the listed ones, and kin_thr is unused.  counts=True: (mask, n_rel, n_div) as the rule saw them; n_rel is None
+        with kin_pairs.  GENESIS::pcairPartition in structure; parity with it is not claimed."""
+        k8 = self._sample_keep(keep)
+        if k8 is None:
+            k8 = np.ones(self.N, dtype=np.uint8)
+        n = C.c_uint64(0)
+        n_div = np.zeros(self.N, dtype=np.uint32)
+        if kin_pairs is None:
+            n_rel = np.zeros(self.N, dtype=np.uint32)
+            check(lib().fpca_pcair_king(self.h, float(kin_thr), float(div_thr), _p(k8), C.byref(n), _p(n_rel), _p(n_div)))
+        else:
+            n_rel = None
+            pi, pj, kin = _kin_pairs(kin_pairs)
+            check(lib().fpca_pcair_pairs(self.h, float(div_thr), pi.size, _p(pi), _p(pj), _p(kin), _p(k8), C.byref(n), _p(n_div)))
+        out = k8 != 0
+        assert int(out.sum()) == n.value
+        return (out, n_rel, n_div) if counts else out
+
+    def bench_king_census(self, reps=5):
+        """fpca_bench_king_census: milliseconds of each of `reps` passes of the census kernel over the whole triangle (bench_king's
+        products, so its MAC count applies)."""
+        ms = np.zeros(int(reps), dtype=np.float64)
+        check(lib().fpca_bench_king_census(self.h, int(reps), _p(ms)))
+        return ms
 
     # ---- relationship matrix ------------------------------------------------------------------------
     def grm_block(self, i0, ni, j0, nj, divisor="shared", counts=False):
@@ -1718,6 +1799,92 @@ def pcrelate_related(prefix, pcs, train=None, thr=2 ** -5.5, min_snps=0, po_k0=0
     # (k0 of the triangle is already the chosen estimator: a switch below every kinship hands it through)
     k0, k1, typ = pcrelate_classify(kin, r["k0"][at], k2, nsnp, k0_switch=-np.finfo(np.float64).max, po_k0=po_k0)
     return dict(i=lo, j=hi, kin=kin, k0=k0, k1=k1, k2=k2, nsnp=nsnp, type=typ)
+
+
+def pcair_partition_rule(N, i, j, kin, n_div, keep=None):
+    """fpca_pcair_partition (host only): PC-AiR's partition rule on caller arrays -- the boolean mask of the samples left when, among those
+    of `keep` (None: all N), one sample at a time goes until no listed pair (i[k], j[k]) remains: the one in most pairs; among equals the
+    one of smallest n_div; among equals the one whose kin over its remaining pairs sums lowest (fp64, in ascending order of the partner's
+    index); among equals the largest index.  Repeated and reversed pairs count once, with the first kin listed."""
+    N = int(N)
+    pi, pj, kin = _kin_pairs((i, j, kin))
+    n_div = np.ascontiguousarray(n_div, dtype=np.uint32)
+    if n_div.shape != (N,):
+        raise ValueError("n_div must have one entry per sample (%d), it has shape %s" % (N, n_div.shape))
+    if keep is None:
+        k8 = np.ones(N, dtype=np.uint8)
+    else:
+        keep = np.asarray(keep)
+        if keep.shape != (N,):
+            raise ValueError("keep must have one entry per sample (%d), it has shape %s" % (N, keep.shape))
+        k8 = np.ascontiguousarray(keep != 0, dtype=np.uint8)
+    n = C.c_uint64(0)
+    check(lib().fpca_pcair_partition(N, pi.size, _p(pi), _p(pj), _p(kin), _p(n_div), _p(k8), C.byref(n)))
+    out = k8 != 0
+    assert int(out.sum()) == n.value
+    return out
+
+
+def _pcair_partition(prefix, kin_thr, div_thr, snps, maf, geno, ld, keep, kin_pairs, device):
+    """(mask, n_rel, n_div, the SNP mask over the .bim rows) of Context.pcair_partition on the selected SNPs of a PLINK fileset."""
+    qc = not (maf <= 0 and geno >= 1)
+    if ld is not None:
+        ld = _ld_args(ld)
+    N = count_fam_rows(prefix + ".fam")
+    with Context.from_bed(prefix + ".bed", N, device=device, accum="fp64") as full:
+        if snps is None and not qc and ld is None:
+            return full.pcair_partition(kin_thr, div_thr, keep=keep, kin_pairs=kin_pairs, counts=True) + (np.ones(full.P, dtype=bool),)
+        sub, mask = _select_snps(full, prefix, snps, qc, maf, geno, ld)
+        with sub:
+            return sub.pcair_partition(kin_thr, div_thr, keep=keep, kin_pairs=kin_pairs, counts=True) + (mask,)
+
+
+def pcair_partition(prefix, kin_thr=2 ** -5.5, div_thr=-2 ** -5.5, snps=None, maf=0.0, geno=1.0, ld=None, keep=None, kin_pairs=None, device=0):
+    """PC-AiR's unrelated set of a PLINK fileset (Context.pcair_partition): a boolean mask over the rows of prefix.fam in which no pair is
+    related -- KING-robust kinship above kin_thr, or, with kin_pairs=(i, j, kin), one of the listed pairs -- chosen so that of two
+    relatives the one with more partners of divergent ancestry (kinship below div_thr) stays.  snps / maf / geno / ld as in king_cutoff():
+    they are applied first, over all samples.  keep: a boolean array with one entry per sample; the partition runs among those.
+    GENESIS::pcairPartition in structure; parity with GENESIS is not claimed."""
+    return _pcair_partition(prefix, kin_thr, div_thr, snps, maf, geno, ld, keep, kin_pairs, device)[0]
+
+
+def pcair(prefix, ndim=10, kin_thr=2 ** -5.5, div_thr=-2 ** -5.5, iterations=1, relate_pcs=None, eps=0.01, snps=None, maf=0.0, geno=1.0,
+          ld=None, keep=None, device=0, **flashpca_kw):
+    """PC-AiR (Conomos, Miller & Thornton 2015) of a PLINK fileset: PCs that describe ancestry and not family structure.  snps / maf / geno
+    / ld select the SNPs (over all samples, as in king_cutoff()); pcair_partition() on them picks the unrelated set, among the samples of
+    keep if given; the PCA runs on the unrelated samples and everyone else is projected -- exactly flashpca(prefix, ndim=ndim,
+    snps=<snps_kept>, keep=<the mask>, **flashpca_kw), whose dict is returned with `unrelated_kept`, `n_rel`, `n_div` (the census the
+    partition saw) and `snps_kept` added; `projection_all` holds every sample's PCs.
+    iterations=2 adds GENESIS's second round: pcrelate_related() on the same SNPs with pcs = projection_all[:, :relate_pcs] (relate_pcs:
+    min(ndim, 4) by default), train = the first mask, thr = kin_thr and eps; its pairs are the relatives of a second partition
+    (kin_pairs=) and a second PCA.  The result is the second round's -- n_rel then counts the PC-Relate pairs per sample -- with the first
+    mask kept as `unrelated_kept_1`.  Not claimed: parity with GENESIS::pcair."""
+    if iterations not in (1, 2):
+        raise ValueError("iterations is 1 (the KING partition) or 2 (a second round on PC-Relate kinship), found %r" % (iterations,))
+    if not isinstance(prefix, str):
+        raise ValueError("pcair() takes a PLINK fileset; the partition is made from its packed genotypes, not from a numeric matrix")
+    for name in ("keep", "snps", "maf", "geno", "ld", "unrelated", "mind", "hwe", "unrelated_min_shared"):
+        if name in flashpca_kw:
+            raise ValueError("%s is not passed on to flashpca() by pcair()" % name)
+    ndim = int(ndim)
+    relate_pcs = min(ndim, 4) if relate_pcs is None else int(relate_pcs)
+    if iterations == 2 and not 0 <= relate_pcs <= ndim:
+        raise ValueError("relate_pcs is between 0 and ndim (%d), found %d" % (ndim, relate_pcs))
+    unrel, n_rel, n_div, snps_kept = _pcair_partition(prefix, kin_thr, div_thr, snps, maf, geno, ld, keep, None, device)
+    r = flashpca(prefix, ndim=ndim, snps=snps_kept, keep=unrel, device=device, **flashpca_kw)
+    first = None
+    if iterations == 2:
+        first = unrel
+        t = pcrelate_related(prefix, r["projection_all"][:, :relate_pcs], train=first, thr=kin_thr, eps=eps, snps=snps_kept, device=device)
+        unrel, _, n_div, _ = _pcair_partition(prefix, kin_thr, div_thr, snps_kept, 0.0, 1.0, None, keep, (t["i"], t["j"], t["kin"]), device)
+        among = np.ones(unrel.size, dtype=bool) if keep is None else np.asarray(keep) != 0
+        both = among[t["i"]] & among[t["j"]]
+        n_rel = (np.bincount(t["i"][both], minlength=unrel.size) + np.bincount(t["j"][both], minlength=unrel.size)).astype(np.uint32)
+        r = flashpca(prefix, ndim=ndim, snps=snps_kept, keep=unrel, device=device, **flashpca_kw)
+    r.update(unrelated_kept=unrel, n_rel=n_rel, n_div=n_div, snps_kept=snps_kept)
+    if first is not None:
+        r["unrelated_kept_1"] = first
+    return r
 
 
 def rel_cutoff(prefix, thr=0.025, divisor="shared", snps=None, maf=0.0, geno=1.0, ld=None, keep=None, device=0):

@@ -27,6 +27,9 @@
 //   king_rel.hip        fpca_king_counts_block / fpca_king_related / fpca_king_cutoff_shared / fpca_king_classify: the relationship table --
 //                       shared calls, IBS0, het-het beside phi (k_king_rel, seven products per pair, a loop of its own), a minimum-shared
 //                       filter in front of king.hip's host rule, the degree / parent-offspring classification on the host
+//   pcair.hip           fpca_king_census / fpca_pcair_partition / fpca_pcair_king / fpca_pcair_pairs: PC-AiR's unrelated set -- per-sample counts
+//                       of related and of ancestry-divergent pairs beside the list of the related ones, from one pass with k_king's
+//                       products (k_king_census: counts reduced in the wave, integer atomics), the partition rule on the host
 //   grm.hip             fpca_grm_block / fpca_grm_tri / fpca_grm_pairs / fpca_grm_cutoff: the relationship matrix X X' / n of the standardised
 //                       genotypes on the same sample-major copy -- the sums on the FP64 MFMA with the per-SNP table staged in LDS (k_grm_dot),
 //                       the shared-call counts as one int8 product (k_grm_shared), the divide and the three outputs (k_grm_finish), in slabs
@@ -358,6 +361,12 @@ void ld_check_window(const char *fn, uint32_t window, uint32_t step); // FPCA_EI
 // n_pairs, all below N; while an edge remains the sample of largest current degree goes, the largest index among equals.  keep[N] in and
 // out (entries become 0 / 1, a 0 stays 0); returns the number left non-zero.
 uint64_t king_cutoff_rule(const uint32_t *i, const uint32_t *j, uint64_t n_pairs, uint64_t N, uint8_t *keep);
+
+// ---- pcair.hip --------------------------------------------------------------------------------------------
+// host only: the rule of fpca_pcair_partition (include/fpca.h).  Edges (i[k], j[k]) with kinship kin[k], k < n_pairs, i != j, all below N
+// (FPCA_EINVAL otherwise); n_div[N]; keep[N] in and out (entries become 0 / 1, a 0 stays 0); returns the number left non-zero.
+uint64_t pcair_partition_rule(uint64_t N, uint64_t n_pairs, const uint32_t *i, const uint32_t *j, const double *kin, const uint32_t *n_div,
+                              uint8_t *keep);
 
 // ---- qc_census.hip ----------------------------------------------------------------------------------------
 // host only: the rules of fpca_sample_qc / fpca_snp_qc_samples (include/fpca.h) on counts by raw code ([.][4]: hom A1, missing, het, hom A2).

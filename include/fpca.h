@@ -293,6 +293,47 @@ int fpca_king_related(fpca_ctx *ctx, const uint8_t *keep /* [N] or NULL */, doub
                       uint32_t *j, double *phi, uint32_t *counts /* [max_pairs][6] */, uint64_t *n_pairs);
 int fpca_king_cutoff_shared(fpca_ctx *ctx, double thr, uint32_t min_shared, uint8_t *keep /* [N] in/out */, uint64_t *n_kept);
 int fpca_king_classify(uint64_t n_pairs, const double *phi, const uint32_t *counts /* [n_pairs][6] */, double po_ibs0, uint8_t *type /* [n_pairs] */);
+/*   PC-AiR's partition (Conomos, Miller & Thornton 2015): an unrelated set chosen by kinship AND by ancestry divergence -- the first half of
+ *   the PC-AiR / PC-Relate pipeline.  A strongly negative phi marks a pair of divergent ancestry; of two relatives the one with more
+ *   divergent partners stays, so that the unrelated set stays representative of every ancestry.
+ *   Over the pairs i < j whose samples both have keep != 0, with phi exactly fpca_king_block's value (the same five integer products, the
+ *   same int64 combination, the same single fp64 divide, NaN where min(het) == 0):
+ *      related     phi > kin_thr
+ *      divergent   phi < div_thr AND not related AND (i, j) not in the caller's exclusion list
+ *   A NaN pair is neither.  kin_thr = +inf is allowed ("no relatives from KING"); kin_thr < div_thr is allowed, related wins; NaN
+ *   thresholds are refused.  n_rel[s] / n_div[s] = the related / divergent pairs that contain sample s; 0 for a sample with keep == 0.
+ *   2^-5.5 and -2^-5.5 are the customary thresholds (GENESIS's defaults).
+ *   The rule, on the host, on the graph whose edges are the related pairs among the samples with keep != 0, each with a kinship `kin`:
+ *      1. while an edge remains, one sample is moved to the related set (keep -> 0);
+ *      2. it is the one of largest current degree;
+ *      3. among equals, the one of smallest n_div (n_div is fixed as given: it is not recomputed as samples leave);
+ *      4. among equals, the one of smallest sum of kin over its CURRENT edges -- in fp64, recomputed from the current edges each time it
+ *         is needed, added in ascending order of the neighbour's index, never maintained by subtraction;
+ *      5. among equals, the one of largest index (fpca_king_cutoff's tie rule).
+ *   Duplicate and reversed pairs count once, with the first kin listed for the pair.  This is GENESIS::pcairPartition in structure; the
+ *   order of the tie-breaks 3 - 5 is written from the paper, and PARITY WITH GENESIS IS NOT CLAIMED (as none is with plink2 or KING above).
+ *   fpca_king_census      n_rel[N] and n_div[N] from ONE pass over the triangle (k_king_census: k_king's products, the counts reduced in
+ *                         the wave and added with integer atomics -- exact, hence the same in any order).  (excl_i[k], excl_j[k]), k <
+ *                         n_excl: pairs never counted divergent, in either order, repeats allowed; FPCA_EINVAL for i == j or an index >= N.
+ *   fpca_pcair_partition  host only, no context: the rule.  (i[k], j[k], kin[k]), k < n_pairs: the edges; n_div[N]; keep[N] in and out
+ *                         (entries become 0 / 1, a 0 stays 0); *n_kept (may be NULL) = entries left non-zero.  FPCA_EINVAL, with keep
+ *                         untouched, for a pair with i == j or an index >= N, a kin that is NaN or infinite, a NULL array and N >= 2^32.
+ *                         Memory linear in N + n_pairs.
+ *   fpca_pcair_king       the census and the list of related pairs (with phi as kin) from ONE fused pass, then the rule.  Room for 2^26
+ *                         related pairs, else FPCA_ENOMEM naming their number.  n_rel / n_div (may be NULL): the census the rule saw.
+ *   fpca_pcair_pairs      relatives from outside (PC-Relate, the GRM): the census with kin_thr = +inf and the given pairs as the exclusion
+ *                         list, then the rule on the given pairs.  n_div (may be NULL): the census the rule saw.
+ *   The three device calls refuse what the calls above refuse, before any device work, make the same sample-major copy and leave the
+ *   context unchanged. */
+int fpca_king_census(fpca_ctx *ctx, const uint8_t *keep /* [N] or NULL */, double kin_thr, double div_thr,
+                     const uint32_t *excl_i, const uint32_t *excl_j, uint64_t n_excl,      /* pairs never counted divergent; may be 0 / NULL */
+                     uint32_t *n_rel /* [N] */, uint32_t *n_div /* [N] */);
+int fpca_pcair_partition(uint64_t N, uint64_t n_pairs, const uint32_t *i, const uint32_t *j, const double *kin,
+                         const uint32_t *n_div /* [N] */, uint8_t *keep /* [N] in/out */, uint64_t *n_kept);   /* host only, no context: the rule */
+int fpca_pcair_king(fpca_ctx *ctx, double kin_thr, double div_thr, uint8_t *keep /* [N] in/out */, uint64_t *n_kept,
+                    uint32_t *n_rel /* [N] or NULL */, uint32_t *n_div /* [N] or NULL */);   /* ONE fused triangle pass, then the rule */
+int fpca_pcair_pairs(fpca_ctx *ctx, double div_thr, uint64_t n_pairs, const uint32_t *i, const uint32_t *j, const double *kin,
+                     uint8_t *keep /* [N] in/out */, uint64_t *n_kept, uint32_t *n_div /* [N] or NULL */);
 
 /* Relationship matrix: the genetic relationship matrix (GRM) of the samples of the resident matrix -- the X X' / P whose eigenvectors
  * fpca_pca computes without forming it -- on the FP64 matrix cores, and a relatedness cutoff on top of it (the purpose of plink

@@ -218,6 +218,10 @@ int fpca_bench_king(fpca_ctx *ctx, int reps, double *ms, double *macs);
 /* the same for the pair kernel of fpca_king_related (scripts/king_rel_measure.py), at thr = 0.0884, min_shared = 0, no keep: seven
  * products per pair of 32-sample blocks on the general path, two where neither block has a missing call. */
 int fpca_bench_king_rel(fpca_ctx *ctx, int reps, double *ms, double *macs);
+/* the same for the census kernel of fpca_pcair_king (k_king_census, scripts/pcair_measure.py): the whole triangle at kin_thr = 2^-5.5,
+ * div_thr = -2^-5.5, no keep, no exclusion list, a pair list of 2^20 slots; the counter and both count arrays are cleared before each
+ * pass, outside the clock.  k_king's products, so fpca_bench_king's MAC count applies. */
+int fpca_bench_king_census(fpca_ctx *ctx, int reps, double *ms);
 /* time the FP64 Gram kernel of the relationship matrix alone (k_grm_dot, scripts/grm_measure.py) over the whole lower triangle, slab by slab as
  * fpca_grm_tri launches it: the sample-major copy, the totals and the slab scratch are ready before the clock starts; one untimed pass,
  * then `reps` passes with a pair of HIP events around each, ms[reps].  *flops (may be NULL): floating-point operations one pass issues
